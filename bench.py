@@ -4,21 +4,26 @@ k = 20, ncv = 40 — on N MI355X of one node (N > 1: the same matrix row-partiti
 xGMI by RCCL before every SpMV = configs[2], strong scaling).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full          # + every figure below the headline
+    python bench.py --gpus 1 --steps 3 --dump-outputs DIR         # + the last step's results as DIR/*.npy
     python bench.py --gpus 8                      # spawns its 8 ranks itself (re-exec through torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
 A "step" is ONE complete solve: init() + compute(LargestMagn, tol) + eigenvectors() with the matrix already
-resident in HBM (generated there by the counter-hash generator of SURVEY.md §8d).  Rank 0 prints one JSON line:
+resident in HBM (generated there by the counter-hash generator of SURVEY.md §8d).  A plain run sets up, warms up, times
+the steps and reports the headline (value, ms_per_step, the in-loop SpMV roofline, the solve); --full adds everything
+else, outside the timed region.  Rank 0 prints one JSON line:
   value      eigenpairs/s of the whole job;
   roofline   the SpMV kernel that ran in the timed region, on the bytes THAT kernel has to move (its storage format's
              values/indices + x + y + the fused epilogue's two vector reads) / its mean launch duration from HIP events
              bound to the dispatches inside the timed region; `traffic` = the PMC-measured HBM bytes per launch of the same
              instantiation (profiles/*pmc_traffic.json); the CSR-int32 byte count of SURVEY.md 8d over the same time is
              reported separately as `csr_equivalent_gbps` (it is NOT an HBM rate when a compressed format ran);
-  secondary  driver-run figures of the other configurations: CSR kernels on the same matrix, M-rand (scattered columns,
+             the live PMC passes and the stand-alone launches run with --full only;
+  secondary  (--full) driver-run figures of the other configurations: CSR kernels on the same matrix, M-rand (scattered columns,
              stand-alone and inside a solver loop), C4 (GenEigsSolver 5M) and C5 (shift-and-invert 2M), all on true bytes;
-  cpu_baseline  the CPU oracle (Eigen-free restatement of the reference, 1 thread like the reference) timed on a bounded
+  cpu_baseline  (--full) the CPU oracle (Eigen-free restatement of the reference, 1 thread like the reference) timed on a bounded
              sample of the same workload.
 """
 import argparse
@@ -57,8 +62,42 @@ def parse():
     p.add_argument("--spmv-reps", type=int, default=50, help="stand-alone SpMV launches timed after the solves")
     p.add_argument("--orth", default=ORTH_DEFAULT, choices=["reference", "onesweep", "onesweep-eager"],
                    help="orthogonalisation of the Lanczos steps in the timed region (include/mispec.h mispec_fac_set_orth_mode); the other "
-                        "mode is timed as well, outside the timed region, and reported as `other_orth_mode`")
+                        "mode is timed as well (with --full), outside the timed region, and reported as `other_orth_mode`")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beyond the headline figure, outside the timed region: the other orthogonalisation mode, "
+                        "host eigenvectors, the per-family kernel split, stand-alone SpMV launches, the live PMC passes, the secondary "
+                        "configurations, the shard proxy, the CPU baseline and (N > 1) the all-gather variant and the wire timers")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64): the eigenvalues and "
+                        "a fixed, seeded sample of the eigenvector rows (with their row indices); e.g. bench_outputs/ (git-ignored)")
     return p.parse_args()
+
+
+DUMP_ROWS = 200_000        # eigenvector rows written by --dump-outputs: 200k x nev 20 x 8 bytes = 32 MB
+DUMP_BYTES = 48 * 2 ** 20  # ... fewer where nev is larger: the sample and its row indices stay within this
+DUMP_SEED = 20261016
+
+
+def dump_outputs(path, eigs, rank):
+    """The arrays a caller of the timed path receives from its last step: the eigenvalues and the eigenvectors (this rank's rows,
+    n x nconv).  The full eigenvector matrix is 1.6 GB at n = 1e7: a fixed, seeded sample of its rows is written, the rows the
+    same for every run of the same size.  Every rank forms its host copy; rank 0 writes."""
+    import numpy as np
+
+    evals = np.asarray(eigs.eigenvalues(), dtype=np.float64)
+    X = eigs.eigenvectors()
+    if rank != 0:
+        return
+    rows = X.shape[0]
+    keep = min(DUMP_ROWS, DUMP_BYTES // (8 * (X.shape[1] + 1)))
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+    else:
+        idx = np.arange(rows)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "eigenvalues.npy"), evals)
+    np.save(os.path.join(path, "eigenvectors_sample.npy"), np.ascontiguousarray(X[idx], dtype=np.float64))
+    np.save(os.path.join(path, "eigenvectors_sample_rows.npy"), idx.astype(np.float64))
 
 
 def respawn_as_ranks(args):
@@ -730,11 +769,13 @@ def main():
     elapsed, total_pairs, prof = timed_steps(eigs, args.steps)
 
     # ---- everything below is outside the timed region -------------------------------------------------
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eigs, rank)
     halo, recv_doubles = eigs.exchange_info()
     # north_star words the exchange as an all-gather of the Krylov vector: when the timed region used the neighbour
     # exchange, the same number of steps is also run with the all-gather and reported next to it
     allgather_run = None
-    if world > 1 and halo:
+    if world > 1 and halo and args.full:
         prev = os.environ.get("MISPEC_EXCHANGE")
         os.environ["MISPEC_EXCHANGE"] = "allgather"
         ag = new_solver(2)
@@ -751,7 +792,7 @@ def main():
     # the wire, timed on its own (profile level 3: HIP events around the exchange on its stream, around the part of it a product
     # waits for, around the all-reduces) in one more solve outside the timed region — flat `wire_*` scalars in the line
     wire = None
-    if world > 1:
+    if world > 1 and args.full:
         we = new_solver(3)
         solve(we)
         w0 = we.get_profile()
@@ -788,7 +829,7 @@ def main():
             rccl_info = [repr(ex)]
     # the other orthogonalisation mode on the same matrix, same number of steps (not part of `value`)
     other_mode = None
-    if True:  # always reported, with or without profiling
+    if args.full:  # reported with or without profiling
         other = "reference" if args.orth.startswith("onesweep") else "onesweep"
         oe = new_solver(0, other)
         solve(oe)
@@ -800,7 +841,7 @@ def main():
         del oe
     # the reference's eigenvectors() hands back a HOST matrix: the same steps with that copy inside the timed loop
     with_host = None
-    if world == 1 and not args.no_profile:
+    if world == 1 and not args.no_profile and args.full:
         barrier()
         t0 = time.perf_counter()
         hp = 0
@@ -825,7 +866,7 @@ def main():
     # per-family kernel split: one more solve with every family instrumented, not part of `value`
     split = None
     pass_only = None
-    if not args.no_profile:
+    if not args.no_profile and args.full:
         full = new_solver(1)
         solve(full)
         split = full.get_profile()
@@ -846,7 +887,8 @@ def main():
     onered_frac = oinfo["one_reduction_steps"] / max(oinfo["lagged_steps"], 1) if oinfo.get("one_reduction") else 0.0
     epi_vectors = 2.0 - onered_frac  # one-reduction steps read one epilogue operand (f~ for <f~, A f~>), the others v_prev and v
     head = spmv_block(op, spmv_ms, prof["n_spmv"], True, epi_vectors)
-    alone_ms = standalone_ms(op, args.n if world == 1 else int(sa.lib().mispec_shard_block(args.n, world)) * world, args.spmv_reps)
+    alone_ms = (standalone_ms(op, args.n if world == 1 else int(sa.lib().mispec_shard_block(args.n, world)) * world, args.spmv_reps)
+                if args.full else None)
 
     transport_name = {"gloo-staged": "gloo (host-staged)", "torch": "torch.distributed (RCCL)"}.get(os.environ.get("MISPEC_COMM", "rccl"), "RCCL")
     if type(getattr(ctx, "_comm", None)).__name__ == "TorchComm":  # (also the fallback when the library's own communicator failed)
@@ -867,8 +909,8 @@ def main():
         traffic, traffic_file = pmc_traffic(args.n, fmt, post_scaled=post_inst) if world == 1 else (None, None)
         if args.orth.startswith("onesweep") and not post_inst and traffic_file and not traffic_file.startswith("r09"):
             traffic, traffic_file = None, None  # (summaries of earlier rounds mix this instantiation's reference-flow launches in)
-        traffic_committed, live_note = traffic, "not attempted (--no-live-pmc or more than one rank)"
-        if world == 1 and not args.no_live_pmc:
+        traffic_committed, live_note = traffic, "not attempted (no --full, --no-live-pmc or more than one rank)"
+        if world == 1 and not args.no_live_pmc and args.full:
             live, live_note = live_pmc_traffic(args.n, fmt, post_inst, modes=args.orth.replace("-eager", ""))
             if live is not None:
                 traffic, traffic_file = live, None
@@ -937,7 +979,7 @@ def main():
                 "csr_equivalent_note": "SURVEY.md 8d's CSR/int32 byte count (12 nnz + 20 n) over the same time: comparable across formats and "
                                        "rounds, but not an HBM rate unless the int32 CSR kernel ran",
                 "standalone_ms_per_launch": alone_ms,
-                "standalone_gbps": op.stored_bytes() / (alone_ms * 1e-3) / 1e9,
+                "standalone_gbps": op.stored_bytes() / (alone_ms * 1e-3) / 1e9 if alone_ms else None,
             },
             "solve": {
                 "nconv": int(total_pairs // args.steps), "num_operations": int(eigs.num_operations()),
@@ -1001,7 +1043,7 @@ def main():
                 out["wire_" + k if not k.startswith("wire_") else k] = wire[k]
         if rccl_info is not None:
             out["rccl_info"] = rccl_info
-        if world == 1 and not args.no_secondary and not args.no_profile:
+        if world == 1 and args.full and not args.no_secondary and not args.no_profile:
             try:
                 out["secondary"] = secondary_configs(args, ctx, op, sa)
             except Exception as e:  # noqa: BLE001 - the headline line must still be printed
@@ -1022,7 +1064,7 @@ def main():
                     "note": "the int32 CSR kernel (x windows in LDS) forced on the headline matrix (mispec_csr_set_spmv_format 0), "
                             "HIP events inside a complete solve; bytes = 12 nnz + 4 (rows+1) + 8 cols + 8 rows + 8 rows per v_prev read; "
                             "csr_kernel_frac above is on SURVEY.md 8d's bytes alone"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, int(eigs.num_operations()), int(total_pairs // args.steps), int(eigs.num_iterations()))
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -1,16 +1,16 @@
 #!/bin/bash
 # Compiles the reference's OWN test programs (/root/reference/test/*.cpp, Catch2 single header included), unmodified and where
 # they lie, against this repository's headers (include/Spectra) — with tests/cpp/eigen_lite standing in for Eigen, which this
-# image does not have — and links them with spectra_amd/libmispec.so.  Outputs: tests/cpp/_ref/<Name>.bin (git-ignored; they
-# travel to the GPU box with the snapshot, the reference's sources do not and are not needed there).
-#   usage: tests/cpp/build_reference_tests.sh [Name ...]      default: every program of the list below
+# image does not have — and links them with spectra_amd/libmispec.so.  Outputs: oracle/_ref/programs/<Name>.bin (git-ignored,
+# like everything under oracle/_ref; they are prebuilt test infrastructure, the reference's sources are not needed to run them).
+#   usage: oracle/build_ref_programs.sh [Name ...]      default: every program of the list below
 # SURVEY.md 8f row 2.  Nothing from /root/reference is copied into the repository.
 set -u
-ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 REF="${MISPEC_REFERENCE_DIR:-/root/reference}"
-OUT="$ROOT/tests/cpp/_ref"
+OUT="$ROOT/oracle/_ref/programs"
 if [ ! -d "$REF/test" ]; then
-    echo "build_reference_tests: $REF/test not found: nothing to do"
+    echo "build_ref_programs: $REF/test not found: nothing to do"
     exit 0
 fi
 mkdir -p "$OUT"
@@ -45,7 +45,7 @@ for name in $LIST; do
         echo "built $name.bin"
         rm -f "$OUT/$name.log"
     else
-        echo "FAILED $name (see tests/cpp/_ref/$name.log)"
+        echo "FAILED $name (see oracle/_ref/programs/$name.log)"
         status=1
     fi
     rm -f "$OUT/$name.o"

@@ -1,6 +1,6 @@
 """the reference's OWN test programs (/root/reference/test/*.cpp with its Catch2 header), compiled
 UNMODIFIED against include/Spectra — tests/cpp/eigen_lite stands in for Eigen, which this image does not have — and linked with
-libmispec.so (tests/cpp/build_reference_tests.sh, run by __graft_entry__.build() where the reference is present).  The binaries
+libmispec.so (oracle/build_ref_programs.sh, run by __graft_entry__.build() where the reference is present).  The binaries
 are built in the container that holds /root/reference and travel to the GPU box; nothing here reads the reference at run time.
 
 Elsewhere: Givens / QR / Eigen / Schur / Orthogonalization.cpp test host-side classes and run without a GPU
@@ -27,10 +27,10 @@ def orth_env(request, monkeypatch):
     return request.param
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "cpp", "_ref")
+REF = os.path.join(ROOT, "oracle", "_ref", "programs")
 PROGRAMS = ["SymEigs", "SymEigsShift", "GenEigs", "GenEigsRealShift", "GenEigsComplexShift", "SymGEigsCholesky", "SymGEigsRegInv",
             "SVD", "DavidsonSymEigs", "Example1", "Example2", "Example3", "Example4",
-            # built with oracle/eigen_shim in Eigen's place (complex and float instantiations, tests/cpp/build_reference_tests.sh)
+            # built with oracle/eigen_shim in Eigen's place (complex and float instantiations, oracle/build_ref_programs.sh)
             "Arnoldi", "SparseSymMatProd", "SparseGenMatProd", "DenseSymMatProd", "DenseGenMatProd"]
 
 
@@ -38,7 +38,7 @@ PROGRAMS = ["SymEigs", "SymEigsShift", "GenEigs", "GenEigsRealShift", "GenEigsCo
 def test_reference_test_program(name):
     exe = os.path.join(REF, name + ".bin")
     if not os.path.exists(exe):
-        pytest.skip("tests/cpp/_ref/%s.bin not built (needs /root/reference at build time)" % name)
+        pytest.skip("oracle/_ref/programs/%s.bin not built (needs the reference's sources at build time)" % name)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     out = r.stdout
     # Example1 (20, 5, 12) exhausts its Krylov space after 10 steps; whether the surviving 1e-15 of noise trips the breakdown clamp

@@ -148,3 +148,38 @@ def test_flat_scalars_the_driver_keeps():
     n, nnz = rec["config"]["n"], rec["config"]["nnz_per_gpu"]
     frac = (12.0 * nnz + 20.0 * n + 4.0) / (want["csr_kernel_ms"] * 1e-3) / 8e12
     assert abs(frac - want["csr_kernel_frac"]) <= 1e-9 and want["secondary_jitter_band_format"] == 0 and want["secondary_stencil_rcm_format"] == 0
+
+
+def test_dump_outputs_is_a_fixed_sample_within_the_budget(tmp_path):
+    # --dump-outputs: the last step's eigenvalues and a seeded sample of its eigenvector rows, float64, the same rows on every run,
+    # at most 64 MB in all whatever nev is
+    import numpy as np
+
+    import bench
+
+    class Eigs:
+        def __init__(self, ncol):
+            self.ncol = ncol
+
+        def eigenvalues(self):
+            return np.arange(self.ncol, dtype=np.float64)
+
+        def eigenvectors(self):
+            return np.asfortranarray(np.arange(3_000_000 * self.ncol, dtype=np.float64).reshape(3_000_000, self.ncol))
+
+    for ncol in (20, 100):
+        a, b = tmp_path / f"a{ncol}", tmp_path / f"b{ncol}"
+        bench.dump_outputs(str(a), Eigs(ncol), 0)
+        bench.dump_outputs(str(b), Eigs(ncol), 0)
+        files = sorted(os.listdir(a))
+        assert files == ["eigenvalues.npy", "eigenvectors_sample.npy", "eigenvectors_sample_rows.npy"]
+        total = 0
+        for f in files:
+            x, y = np.load(a / f), np.load(b / f)
+            assert x.dtype == np.float64 and np.array_equal(x, y), f
+            total += x.nbytes
+        assert total <= 64 * 2 ** 20
+        rows, X = np.load(a / "eigenvectors_sample_rows.npy").astype(np.int64), np.load(a / "eigenvectors_sample.npy")
+        assert np.all(np.diff(rows) > 0) and np.array_equal(X, Eigs(ncol).eigenvectors()[rows])
+    bench.dump_outputs(str(tmp_path / "other_rank"), Eigs(20), 1)
+    assert not (tmp_path / "other_rank").exists()

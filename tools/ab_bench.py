@@ -1,4 +1,4 @@
-"""Same-box A/B of environment switches on the headline workload: runs `bench.py --no-secondary --no-cpu-baseline` once per
+"""Same-box A/B of environment switches on the headline workload: runs `bench.py --full --no-secondary --no-cpu-baseline` once per
 variant (each in its own process: the switches are read at library / matrix construction) and prints one line per variant.
 
     python tools/ab_bench.py [--steps K] NAME=ENV1=v,ENV2=v ...     e.g.  base= host_steps=MISPEC_HOST_STEPS=1
@@ -25,7 +25,7 @@ for spec in args:
             continue
         k, _, v = kv.partition("=")
         env[k] = v
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "1", "--no-secondary", "--no-cpu-baseline"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

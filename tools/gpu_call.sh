@@ -3,6 +3,7 @@
 # summaries worth keeping are copied to profiles/ by hand).
 #   gpurun --timeout 1500 -- 'bash tools/gpu_call.sh <what> <tag> [args...]'
 WHAT=$1; TAG=${2:-r05}; shift 2
+REPO="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
@@ -14,8 +15,8 @@ case $WHAT in
     timeout 1200 python tools/ab_bench.py --steps $STEPS "$@" > $OUT/ab.jsonl 2> $OUT/ab.err; cut -c1-600 $OUT/ab.jsonl; tail -3 $OUT/ab.err ;;
   bench)        # bench <tag> [bench.py args]: the driver's command + a rocprofv3 kernel trace of the same command (secondary
                 # configurations included, so that every figure of the line has its kernels in the stats; CPU baseline left out)
-    timeout 900 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err; tail -c 800 $OUT/bench.json; tail -5 $OUT/bench.err
-    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --no-cpu-baseline "$@" > $GRAFT_REPO_ROOT/$OUT/bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$OUT/rocprof.err)
+    timeout 900 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err; tail -c 800 $OUT/bench.json; tail -5 $OUT/bench.err
+    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof -o bench -- python $REPO/bench.py --full --steps 2 --no-cpu-baseline "$@" > $REPO/$OUT/bench_under_rocprof.json 2> $REPO/$OUT/rocprof.err)
     find $OUT/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/bench_kernel_stats.csv
     rm -rf $OUT/prof; head -12 $OUT/bench_kernel_stats.csv ;;
   trace)        # trace <tag> <script> [args]: rocprofv3 kernel trace + stats of a python script
