@@ -4,9 +4,9 @@
  * operator / solver and the Buckling / Cayley modes of the generalized shift solver.  They were
  * built in rounds 1-2 and are kept working, but they are not part of the thin shim the hot path
  * needs: include/mispec.h alone is that shim.
- * Where they live (round 6): the Davidson solver and the complex factorisation (mispec_davidson_*,
- * mispec_zdense_*, mispec_zfac_*: their own kernels, nothing in the hot path calls them) are in a
- * library of their own, spectra_amd/libmispec_extras.so, built on libmispec.so — link -lmispec_extras
+ * Where they live (round 6): the Davidson solver, the complex factorisation and the complex Hermitian
+ * eigensolver (mispec_davidson_*, mispec_zdense_*, mispec_zcsr_*, mispec_zfac_*, mispec_hermeigs_*: their
+ * own kernels, nothing in the real hot path calls them) are in a library of their own, spectra_amd/libmispec_extras.so, built on libmispec.so — link -lmispec_extras
  * -lmispec.  The dense operators and the shift variants share objects with the hot path (the dense
  * GEMV applies the last level of the banded shift solve) and stay in libmispec.so.
  * Conventions (handles, error codes, ownership) as in mispec.h.
@@ -127,6 +127,53 @@ int mispec_zfac_f_norm(const mispec_zfac* F, double* out);
 int mispec_zfac_get_H(const mispec_zfac* F, double* H_host);            /* ncv x ncv, column-major */
 int mispec_zfac_get_V(const mispec_zfac* F, int ncols, double* V_host); /* n x ncols, column-major */
 int mispec_zfac_get_f(const mispec_zfac* F, double* f_host);
+
+/* ---------------------------------------------------------------------------
+ * Complex Hermitian sparse operator — replaces MatOp/SparseHermMatProd.h (y = mat.selfadjointView<Uplo>() * x) for
+ * std::complex<double>.  outer / inner are the compressed index arrays (int32 when index_bytes == 4, int64 when 8; narrowed to int32
+ * at ingest, rejected if they do not fit), values the nnz complex entries; row_major != 0: CSR, else CSC.  Only the `uplo` ('L' / 'U')
+ * triangle is read: it is mirrored conjugated into full CSR in HBM, the diagonal taken real.
+ * ------------------------------------------------------------------------- */
+typedef struct mispec_zcsr mispec_zcsr;
+int mispec_zcsr_upload(mispec_ctx* ctx, int64_t rows, int64_t cols, const void* outer, const void* inner, int index_bytes,
+                       const double* values, int row_major, char uplo, mispec_zcsr** out);
+int mispec_zcsr_destroy(mispec_zcsr* A);
+int64_t mispec_zcsr_rows(const mispec_zcsr* A);
+int64_t mispec_zcsr_cols(const mispec_zcsr* A);
+int64_t mispec_zcsr_nnz(const mispec_zcsr* A);                                          /* stored entries after the mirroring */
+int mispec_zcsr_spmv_host(const mispec_zcsr* A, const double* x_host, double* y_host); /* literal perform_op */
+int mispec_zcsr_coeff(const mispec_zcsr* A, int64_t i, int64_t j, double* out_re_im); /* operator()(i, j) of the mirrored matrix */
+/* average ms of `reps` back-to-back products with lanes_per_row = 4, 8 or 16 lanes per row (0 = the default); benchmark helper */
+int mispec_zcsr_spmv_time(const mispec_zcsr* A, int lanes_per_row, int reps, float* ms_per_launch);
+
+/* Factorisation whose operator is the device complex sparse matrix (every product stays in HBM). */
+int mispec_zfac_create_csr(mispec_ctx* ctx, const mispec_zcsr* A, int ncv, int hermitian, mispec_zfac** out);
+/* The restart of HermEigsBase.h:105-155: the new ncv x ncv H from the host; then V[:, :k+1] <- V Q[:, :k+1] for a real ncv x ncv
+ * column-major Q (Arnoldi.h:312-340 compress_V), f <- f Q(ncv-1, k-1) + V[:, k] H(k, k-1), beta = |f|, subspace dimension k. */
+int mispec_zfac_set_H(mispec_zfac* F, const double* H_host);
+int mispec_zfac_compress_real(mispec_zfac* F, const double* Q_host, int k);
+/* X = V Y for a real ncv x nvec column-major Y: n x nvec complex, column-major, into X_host */
+int mispec_zfac_ritz_vectors(mispec_zfac* F, const double* Y_host, int nvec, double* X_host);
+/* benchmark helper on a full ncv-step factorisation: average ms of `reps` launches of which = 0: X^H y (both stages) over the first
+ * ncols columns of V and y = f; which = 1: the in-place V Q kernel writing ncols columns (Q = I, V unchanged) */
+int mispec_zfac_kernel_time(mispec_zfac* F, int which, int ncols, int reps, float* ms_per_launch);
+
+/* ---------------------------------------------------------------------------
+ * HermEigsSolver<OpType> for std::complex<double> (HermEigsSolver.h, HermEigsBase.h) behind handles, for bindings: the operator is a
+ * device complex sparse matrix or a device dense Hermitian matrix (mispec_zdense_upload with uplo 'L' / 'U').  selection / sorting are
+ * SortRule values (the five symmetric rules); eigenvalues are real, eigenvectors complex (n x nvec, column-major, interleaved).
+ * ------------------------------------------------------------------------- */
+typedef struct mispec_hermeigs mispec_hermeigs;
+int mispec_hermeigs_create_csr(mispec_ctx* ctx, const mispec_zcsr* A, int64_t nev, int64_t ncv, mispec_hermeigs** out);
+int mispec_hermeigs_create_dense(mispec_ctx* ctx, const mispec_zdense* D, int64_t nev, int64_t ncv, mispec_hermeigs** out);
+int mispec_hermeigs_destroy(mispec_hermeigs* S);
+int mispec_hermeigs_init(mispec_hermeigs* S, const double* v0_host); /* v0_host == NULL: SimpleRandom<complex>(0) */
+int mispec_hermeigs_compute(mispec_hermeigs* S, int selection, int64_t maxit, double tol, int sorting, int64_t* nconv);
+int mispec_hermeigs_info(const mispec_hermeigs* S);
+int64_t mispec_hermeigs_num_iterations(const mispec_hermeigs* S);
+int64_t mispec_hermeigs_num_operations(const mispec_hermeigs* S);
+int mispec_hermeigs_eigenvalues(const mispec_hermeigs* S, double* out_host, int64_t* count);
+int mispec_hermeigs_eigenvectors(const mispec_hermeigs* S, int64_t nvec, double* out_host, int64_t* ncols);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,8 @@ from ._capi import MispecError, Profile, build_library, check, lib
 
 __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatProd", "SparseSymShiftSolve", "SymEigsSolver",
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
-           "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED"]
+           "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
+           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -1400,6 +1401,191 @@ class DenseCholesky(SparseCholesky):
 
     def __init__(self, mat, uplo="L", ctx=None):
         super().__init__(_dense_as_csc(mat, "DenseCholesky"), uplo, ctx)
+
+
+def _c128(a):
+    return np.ascontiguousarray(a, dtype=np.complex128)
+
+
+def _zdp(a):
+    """A complex128 array as the interleaved (re, im) double* of include/mispec_extras.h."""
+    return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+
+
+def _uplo_code(uplo):
+    if uplo not in ("L", "U"):
+        raise ValueError("uplo must be 'L' or 'U'")
+    return uplo.encode()
+
+
+class SparseHermMatProd:
+    """MatOp/SparseHermMatProd.h for std::complex<double>: y = A x for a complex Hermitian sparse A of which only the `uplo`
+    triangle of `mat` (a scipy sparse matrix, CSR or CSC kept as given, int32 or int64 indices) is read; it is mirrored conjugated
+    into full CSR in HBM, the diagonal taken real (mispec_zcsr)."""
+
+    def __init__(self, mat, uplo="L", ctx=None):
+        import scipy.sparse as sp
+
+        self.ctx = ctx or default_context()
+        if not sp.issparse(mat):
+            raise ValueError("SparseHermMatProd: a scipy sparse matrix is expected")
+        if mat.format not in ("csr", "csc"):
+            mat = mat.tocsc()
+        if mat.shape[0] != mat.shape[1]:
+            raise ValueError("SparseHermMatProd: matrix must be square")
+        itype = np.int64 if mat.indptr.dtype == np.int64 or mat.indices.dtype == np.int64 else np.int32
+        outer = np.ascontiguousarray(mat.indptr, dtype=itype)
+        inner = np.ascontiguousarray(mat.indices, dtype=itype)
+        vals = _c128(mat.data)
+        h = C.c_void_p()
+        check(lib().mispec_zcsr_upload(self.ctx.h, mat.shape[0], mat.shape[1], outer.ctypes.data, inner.ctypes.data,
+                                       outer.dtype.itemsize, _zdp(vals), int(mat.format == "csr"), _uplo_code(uplo), C.byref(h)))
+        self.h = h
+
+    def rows(self):
+        return lib().mispec_zcsr_rows(self.h)
+
+    def cols(self):
+        return lib().mispec_zcsr_cols(self.h)
+
+    def nnz(self):
+        """Stored entries of the mirrored (full) matrix."""
+        return lib().mispec_zcsr_nnz(self.h)
+
+    def perform_op(self, x_in, y_out=None):
+        """y_out = A * x_in with HOST arrays (the reference's perform_op contract), complex128."""
+        x = _c128(x_in)
+        if x.shape != (self.cols(),):
+            raise ValueError("perform_op: x_in must have cols() entries")
+        y = np.empty(self.rows(), dtype=np.complex128) if y_out is None else y_out
+        check(lib().mispec_zcsr_spmv_host(self.h, _zdp(x), _zdp(y)))
+        return y
+
+    def __matmul__(self, X):
+        X = np.asarray(X, dtype=np.complex128)
+        if X.ndim == 1:
+            return self.perform_op(X)
+        return np.stack([self.perform_op(X[:, j]) for j in range(X.shape[1])], axis=1)
+
+    def __call__(self, i, j):
+        v = np.zeros(2)
+        check(lib().mispec_zcsr_coeff(self.h, int(i), int(j), _dp(v)))
+        return complex(v[0], v[1])
+
+    def spmv_time(self, reps, lanes_per_row=0):
+        """Average ms of `reps` back-to-back device products (lanes_per_row 4 / 8 / 16, 0 = the default)."""
+        ms = C.c_float()
+        check(lib().mispec_zcsr_spmv_time(self.h, int(lanes_per_row), int(reps), C.byref(ms)))
+        return ms.value
+
+    def algorithmic_bytes(self):
+        """Bytes one product must move: 20 per stored entry (16-byte value, 4-byte column), the row pointers, x and y once."""
+        n = self.rows()
+        return 20.0 * self.nnz() + 4.0 * (n + 1) + 16.0 * n + 16.0 * n
+
+    def __del__(self):
+        try:
+            lib().mispec_zcsr_destroy(self.h)
+        except Exception:
+            pass
+
+
+class DenseHermMatProd:
+    """MatOp/DenseHermMatProd.h for std::complex<double>: y = A x for a complex Hermitian dense A of which only the `uplo`
+    triangle is read (mirrored conjugated in HBM, the diagonal taken real; mispec_zdense)."""
+
+    def __init__(self, mat, uplo="L", ctx=None):
+        self.ctx = ctx or default_context()
+        M = np.asarray(mat, dtype=np.complex128)
+        if M.ndim != 2 or M.shape[0] != M.shape[1]:
+            raise ValueError("DenseHermMatProd: a square 2-d array is expected")
+        row_major = M.flags.c_contiguous and not M.flags.f_contiguous
+        if not (M.flags.c_contiguous or M.flags.f_contiguous):
+            M = np.asfortranarray(M)
+        h = C.c_void_p()
+        check(lib().mispec_zdense_upload(self.ctx.h, M.shape[0], M.shape[1], _zdp(M), max(int(M.shape[0]), 1), int(row_major),
+                                         _uplo_code(uplo), C.byref(h)))
+        self.h = h
+
+    def rows(self):
+        return lib().mispec_zdense_rows(self.h)
+
+    def cols(self):
+        return lib().mispec_zdense_cols(self.h)
+
+    def perform_op(self, x_in, y_out=None):
+        x = _c128(x_in)
+        if x.shape != (self.cols(),):
+            raise ValueError("perform_op: x_in must have cols() entries")
+        y = np.empty(self.rows(), dtype=np.complex128) if y_out is None else y_out
+        check(lib().mispec_zdense_gemv_host(self.h, _zdp(x), _zdp(y)))
+        return y
+
+    def __call__(self, i, j):
+        v = np.zeros(2)
+        check(lib().mispec_zdense_coeff(self.h, int(i), int(j), _dp(v)))
+        return complex(v[0], v[1])
+
+    def __del__(self):
+        try:
+            lib().mispec_zdense_destroy(self.h)
+        except Exception:
+            pass
+
+
+class HermEigsSolver:
+    """HermEigsSolver.h for std::complex<double> over SparseHermMatProd / DenseHermMatProd: the methods of SymEigsSolver;
+    eigenvalues() are real (float64), eigenvectors() complex128 (n x nconv)."""
+
+    def __init__(self, op, nev, ncv):
+        h = C.c_void_p()
+        if isinstance(op, SparseHermMatProd):
+            check(lib().mispec_hermeigs_create_csr(op.ctx.h, op.h, int(nev), int(ncv), C.byref(h)))
+        elif isinstance(op, DenseHermMatProd):
+            check(lib().mispec_hermeigs_create_dense(op.ctx.h, op.h, int(nev), int(ncv), C.byref(h)))
+        else:
+            raise TypeError("HermEigsSolver: op must be a SparseHermMatProd or a DenseHermMatProd")
+        self.op, self.h = op, h
+        self.nev, self.ncv = int(nev), int(ncv)
+
+    def init(self, init_resid=None):
+        v0 = None if init_resid is None else _c128(init_resid)
+        if v0 is not None and v0.shape != (self.op.rows(),):
+            raise ValueError("init: the initial residual vector must have n entries")
+        check(lib().mispec_hermeigs_init(self.h, _zdp(v0)))
+
+    def compute(self, selection=SortRule.LargestMagn, maxit=1000, tol=1e-10, sorting=SortRule.LargestAlge):
+        nconv = C.c_int64()
+        check(lib().mispec_hermeigs_compute(self.h, int(selection), int(maxit), float(tol), int(sorting), C.byref(nconv)))
+        return nconv.value
+
+    def info(self):
+        return CompInfo(lib().mispec_hermeigs_info(self.h))
+
+    def num_iterations(self):
+        return lib().mispec_hermeigs_num_iterations(self.h)
+
+    def num_operations(self):
+        return lib().mispec_hermeigs_num_operations(self.h)
+
+    def eigenvalues(self):
+        out = np.empty(self.nev)
+        cnt = C.c_int64()
+        check(lib().mispec_hermeigs_eigenvalues(self.h, _dp(out), C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def eigenvectors(self, nvec=None):
+        nvec = self.nev if nvec is None else int(nvec)
+        out = np.empty((self.op.rows(), max(min(nvec, self.nev), 1)), dtype=np.complex128, order="F")
+        cnt = C.c_int64()
+        check(lib().mispec_hermeigs_eigenvectors(self.h, nvec, _zdp(out), C.byref(cnt)))
+        return out[:, :cnt.value]
+
+    def __del__(self):
+        try:
+            lib().mispec_hermeigs_destroy(self.h)
+        except Exception:
+            pass
 
 
 def hess_qr(H, shift):

@@ -10,7 +10,7 @@ import subprocess
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmispec.so")
 EXTRAS_LIB_PATH = os.path.join(_PKG, "libmispec_extras.so")  # Davidson solver, complex factorisation (mispec_extras.h)
-EXTRAS_PREFIXES = ("mispec_davidson_", "mispec_zdense_", "mispec_zfac_")
+EXTRAS_PREFIXES = ("mispec_davidson_", "mispec_zdense_", "mispec_zfac_", "mispec_zcsr_", "mispec_hermeigs_")
 CSRC = os.path.join(_PKG, "csrc")
 
 MISPEC_OK, MISPEC_EINVAL, MISPEC_ELOGIC, MISPEC_ERUNTIME = 0, -1, -2, -3
@@ -141,6 +141,30 @@ SIGNATURES = {
     "mispec_zfac_get_H": (C.c_int, [_vp, _dp]),
     "mispec_zfac_get_V": (C.c_int, [_vp, C.c_int, _dp]),
     "mispec_zfac_get_f": (C.c_int, [_vp, _dp]),
+    "mispec_zfac_create_csr": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vpp]),
+    "mispec_zfac_set_H": (C.c_int, [_vp, _dp]),
+    "mispec_zfac_compress_real": (C.c_int, [_vp, _dp, C.c_int]),
+    "mispec_zfac_ritz_vectors": (C.c_int, [_vp, _dp, C.c_int, _dp]),
+    "mispec_zfac_kernel_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    # complex Hermitian sparse operator and solver (mispec_extras.h)
+    "mispec_zcsr_upload": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int, _dp, C.c_int, C.c_char, _vpp]),
+    "mispec_zcsr_destroy": (C.c_int, [_vp]),
+    "mispec_zcsr_rows": (C.c_int64, [_vp]),
+    "mispec_zcsr_cols": (C.c_int64, [_vp]),
+    "mispec_zcsr_nnz": (C.c_int64, [_vp]),
+    "mispec_zcsr_spmv_host": (C.c_int, [_vp, _dp, _dp]),
+    "mispec_zcsr_coeff": (C.c_int, [_vp, C.c_int64, C.c_int64, _dp]),
+    "mispec_zcsr_spmv_time": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mispec_hermeigs_create_csr": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vpp]),
+    "mispec_hermeigs_create_dense": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vpp]),
+    "mispec_hermeigs_destroy": (C.c_int, [_vp]),
+    "mispec_hermeigs_init": (C.c_int, [_vp, _dp]),
+    "mispec_hermeigs_compute": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_double, C.c_int, _lp]),
+    "mispec_hermeigs_info": (C.c_int, [_vp]),
+    "mispec_hermeigs_num_iterations": (C.c_int64, [_vp]),
+    "mispec_hermeigs_num_operations": (C.c_int64, [_vp]),
+    "mispec_hermeigs_eigenvalues": (C.c_int, [_vp, _dp, _lp]),
+    "mispec_hermeigs_eigenvectors": (C.c_int, [_vp, C.c_int64, _dp, _lp]),
     "mispec_dense_destroy": (C.c_int, [_vp]),
     "mispec_dense_rows": (C.c_int64, [_vp]),
     "mispec_dense_cols": (C.c_int64, [_vp]),

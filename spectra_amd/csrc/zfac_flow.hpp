@@ -18,6 +18,10 @@
 //   void scale_copy(cd* dst_dev, const cd* src_dev, double alpha);            dst = alpha * src
 //   void axpy(cd* y_dev, cd a, const cd* x_dev);                              y += a x
 //   double norm(const cd* x_dev);   double absmax(const cd* x_dev);   void zero(cd* x_dev);
+// and, only for the restart primitives of the Hermitian solver (compress_real, ritz_vectors — members a backend without it never
+// instantiates):
+//   void vq(const cd* V_dev, int64_t ldv, int m, const double* Q_host, int ldq, int ncols, int first_nnz, cd* out_dev, int64_t ldo);
+//        out[:, c] = V[:, :nnz] Q[:nnz, c] with nnz = min(m, first_nnz + c), for c < ncols; out may be V (in place)
 #pragma once
 
 #include <algorithm>
@@ -344,6 +348,31 @@ public:
         m_k = to_m;
     }
 
+    // The restart of the Hermitian solver (reference HermEigsBase.h:105-155 over Lanczos.h / Arnoldi.h): the host ran the shifted QR
+    // sweeps on Re(H) and hands back the new H (m x m, column-major) ...
+    void set_H(const cd* H_host) { std::copy(H_host, H_host + m_H.size(), m_H.begin()); }
+
+    // ... and the accumulated real orthogonal Q (m x m, column-major): compress_V (Arnoldi.h:312-340) V[:, :k+1] <- V Q[:, :k+1], column
+    // i using the first m - k + i + 1 rows of Q, then f <- f Q(m-1, k-1) + V[:, k] H(k, k-1), beta = |f|; the subspace dimension
+    // becomes k.  Needs a full m-step factorisation.
+    void compress_real(const double* Q, int k)
+    {
+        if (k < 1 || k >= m_m)
+            throw std::invalid_argument("complex factorisation: compress needs 1 <= k < m");
+        if (m_k != m_m)
+            throw std::invalid_argument("complex factorisation: compress needs a full m-step factorisation");
+        m_be.vq(m_V, m_n, m_m, Q, m_m, k + 1, m_m - k + 1, m_V, m_n);
+        m_be.scale_copy(m_f, m_f, Q[size_t(k - 1) * m_m + (m_m - 1)]);
+        m_be.axpy(m_f, H(k, k - 1), col(k));
+        m_beta = m_be.norm(m_f);
+        m_k = k;
+    }
+
+    // X = V Y for a real m x nvec Y (column-major): the Ritz vectors (reference HermEigsBase.h:447-466, matrix_V() * ritz_vec_conv)
+    void ritz_vectors(const double* Y, int nvec, cd* X_dev) { m_be.vq(m_V, m_n, m_m, Y, m_m, nvec, m_m, X_dev, m_n); }
+
+    cd* basis() const { return m_V; }     // the backend's V (n x m) and f, for benchmark helpers
+    cd* residual() const { return m_f; }
     int subspace_dim() const { return m_k; }
     double f_norm() const { return m_beta; }
     int64_t rows() const { return m_n; }

@@ -53,3 +53,40 @@ def stencil7(m, seed=0):
     A = (sp.tril(A) + sp.tril(A, -1).T).tocsr()
     A.sort_indices()
     return A
+
+
+_M1, _M2, _M3, _M4 = (np.uint64(v) for v in (0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB, 0xD6E8FEB86659FD93))
+
+
+def _mix64(z):
+    z = z + _M1
+    z = (z ^ (z >> np.uint64(30))) * _M2
+    z = (z ^ (z >> np.uint64(27))) * _M3
+    return z ^ (z >> np.uint64(31))
+
+
+def hash_value(seed, a, b):
+    """U(-0.5, 0.5) from the splitmix64-style counter hash of the synthetic matrices, for uint64 arrays a, b."""
+    with np.errstate(over="ignore"):
+        k = _mix64(_mix64(np.uint64(seed) ^ a) ^ (b * _M4))
+    return (k >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0) - 0.5
+
+
+def herm_band(n, seed=20240607, offsets=BAND_OFFSETS):
+    """The complex Hermitian M-band: the LOWER triangle (CSR, complex128) of the matrix with M-band's offsets, entry (r, r - off)
+    = h(seed, r - off, r) + i h(seed + 1, r - off, r) with independent counter hashes for the two parts, and a real diagonal
+    h(seed, r, r).  HermEigsSolver / SparseHermMatProd(uplo="L") read exactly this triangle."""
+    r_all = np.arange(n, dtype=np.uint64)
+    rows, cols, vals = [r_all], [r_all], [hash_value(seed, r_all, r_all).astype(np.complex128)]
+    for off in offsets:
+        if off >= n:
+            continue
+        r = r_all[off:]
+        c = r - np.uint64(off)
+        rows.append(r)
+        cols.append(c)
+        vals.append(hash_value(seed, c, r) + 1j * hash_value(seed + 1, c, r))
+    L = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows).astype(np.int64), np.concatenate(cols).astype(np.int64))),
+                      shape=(n, n)).tocsr()
+    L.sort_indices()
+    return L

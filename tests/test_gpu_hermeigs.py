@@ -1,0 +1,147 @@
+"""HermEigsSolver for complex Hermitian matrices (include/Spectra/HermEigsSolver.h, internal/ComplexHermEigs.h behind
+mispec_hermeigs_*), modelled on the reference's test/HermEigs.cpp: dense and sparse cases of its sizes, all five selection rules,
+checked against numpy.linalg.eigh with the reference's bar ||AU - UD||_inf <= 1e-9."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import spectra_amd as sa
+from spectra_amd import workloads
+
+pytestmark = pytest.mark.gpu
+
+RULES = [sa.SortRule.LargestMagn, sa.SortRule.LargestAlge, sa.SortRule.SmallestMagn, sa.SortRule.SmallestAlge, sa.SortRule.BothEnds]
+
+
+def dense_data(n, seed):
+    rng = np.random.default_rng(seed)
+    M = rng.uniform(-1, 1, (n, n)) + 1j * rng.uniform(-1, 1, (n, n))
+    return M + M.conj().T
+
+
+def sparse_data(n, prob, seed):
+    """Like the reference's gen_sparse_data: entries with probability prob, U(-0.5, 0.5) parts, real diagonal; the whole square is
+    filled but only the lower triangle is read."""
+    rng = np.random.default_rng(seed)
+    mask = rng.uniform(size=(n, n)) < prob
+    r, c = np.nonzero(mask)
+    v = rng.uniform(-0.5, 0.5, r.size) + 1j * np.where(r == c, 0.0, rng.uniform(-0.5, 0.5, r.size))
+    return sp.csc_matrix((v, (r, c)), shape=(n, n))
+
+
+def hermitian_from_lower(A):
+    A = A.toarray() if sp.issparse(A) else np.asarray(A)
+    L = np.tril(A, -1)
+    return L + L.conj().T + np.diag(np.diag(A).real)
+
+
+def expected(full, k, rule):
+    w = np.linalg.eigvalsh(full)
+    if rule == sa.SortRule.LargestMagn:
+        sel = w[np.argsort(-np.abs(w))[:k]]
+    elif rule == sa.SortRule.LargestAlge:
+        sel = w[-k:]
+    elif rule == sa.SortRule.SmallestMagn:
+        sel = w[np.argsort(np.abs(w))[:k]]
+    elif rule == sa.SortRule.SmallestAlge:
+        sel = w[:k]
+    else:
+        sel = np.concatenate([w[: k // 2], w[len(w) - (k - k // 2):]])
+    return np.sort(sel)[::-1]  # sorting = LargestAlge
+
+
+def solve_and_check(op, full, k, m, rule):
+    eigs = sa.HermEigsSolver(op, k, m)
+    eigs.init()
+    nconv = eigs.compute(rule)
+    assert eigs.info() == sa.CompInfo.Successful and nconv == k, (eigs.info(), nconv)
+    assert eigs.num_iterations() >= 1 and eigs.num_operations() >= m
+    evals, U = eigs.eigenvalues(), eigs.eigenvectors()
+    assert evals.dtype == np.float64 and U.dtype == np.complex128 and U.shape == (full.shape[0], k)
+    assert np.abs(full @ U - U * evals).max() <= 1e-9
+    assert np.abs(evals - expected(full, k, rule)).max() <= 1e-9
+    assert np.abs(U.conj().T @ U - np.eye(k)).max() <= 1e-10
+    return evals
+
+
+@pytest.mark.parametrize("rule", RULES, ids=lambda r: r.name)
+@pytest.mark.parametrize("n,k,m", [(10, 3, 6), (100, 10, 20), (1000, 20, 50)])
+def test_dense_hermitian(ctx, n, k, m, rule):
+    A = dense_data(n, seed=n)
+    solve_and_check(sa.DenseHermMatProd(A, "L", ctx), hermitian_from_lower(A), k, m, rule)
+
+
+@pytest.mark.parametrize("rule", RULES, ids=lambda r: r.name)
+@pytest.mark.parametrize("n,prob,k,m", [(10, 0.5, 3, 6), (100, 0.1, 10, 20), (1000, 0.01, 20, 50)])
+def test_sparse_hermitian(ctx, n, prob, k, m, rule):
+    A = sparse_data(n, prob, seed=n)
+    solve_and_check(sa.SparseHermMatProd(A, "L", ctx), hermitian_from_lower(A), k, m, rule)
+
+
+def test_storage_variants_give_the_same_eigenvalues(ctx):
+    n, k, m = 300, 8, 24
+    A = sparse_data(n, 0.05, seed=4)
+    full = hermitian_from_lower(A)
+    L = sp.csc_matrix(np.tril(full))
+    U = sp.csc_matrix(np.triu(full))
+
+    def run(op):
+        e = sa.HermEigsSolver(op, k, m)
+        e.init()
+        assert e.compute(sa.SortRule.LargestAlge) == k
+        return e.eigenvalues()
+
+    ref = run(sa.SparseHermMatProd(A, "L", ctx))  # garbage in the strict upper triangle of A is never read
+    assert np.abs(ref - expected(full, k, sa.SortRule.LargestAlge)).max() <= 1e-9
+    for op in (sa.SparseHermMatProd(L, "L", ctx), sa.SparseHermMatProd(L.tocsr(), "L", ctx), sa.SparseHermMatProd(U, "U", ctx),
+               sa.SparseHermMatProd(U.tocsr(), "U", ctx)):
+        assert np.array_equal(run(op), ref)
+    garbage = np.triu(np.full((n, n), 7 - 3j), 1)
+    d_ref = run(sa.DenseHermMatProd(np.tril(full), "L", ctx))
+    assert np.array_equal(run(sa.DenseHermMatProd(np.tril(full) + garbage, "L", ctx)), d_ref)
+    assert np.array_equal(run(sa.DenseHermMatProd(np.ascontiguousarray(np.triu(full)), "U", ctx)), d_ref)
+    assert np.abs(d_ref - ref).max() <= 1e-10
+
+
+def test_zero_imaginary_parts_match_the_real_solver(ctx):
+    n, k, m = 1000, 20, 50
+    rng = np.random.default_rng(9)
+    R = sp.random(n, n, density=0.01, format="csc", random_state=rng, data_rvs=lambda s: rng.uniform(-0.5, 0.5, s))
+    R = (sp.tril(R) + sp.diags(rng.uniform(-0.5, 0.5, n))).tocsc()
+    real = sa.SymEigsSolver(sa.SparseSymMatProd(R), k, m)
+    real.init()
+    assert real.compute(sa.SortRule.LargestAlge) == k
+    herm = sa.HermEigsSolver(sa.SparseHermMatProd(R.astype(np.complex128), "L", ctx), k, m)
+    herm.init()
+    assert herm.compute(sa.SortRule.LargestAlge) == k
+    assert np.abs(herm.eigenvalues() - real.eigenvalues()).max() <= 1e-10
+
+
+def test_user_start_vector_and_argument_checks(ctx):
+    n = 50
+    A = dense_data(n, seed=1)
+    op = sa.DenseHermMatProd(A, "L", ctx)
+    with pytest.raises(ValueError, match="nev must satisfy"):
+        sa.HermEigsSolver(op, 0, 10)
+    with pytest.raises(ValueError, match="ncv must satisfy"):
+        sa.HermEigsSolver(op, 10, 10)
+    e = sa.HermEigsSolver(op, 4, 12)
+    e.init(np.ones(n, dtype=np.complex128))
+    assert e.compute(sa.SortRule.LargestMagn) == 4
+    full = hermitian_from_lower(A)
+    assert np.abs(e.eigenvalues() - expected(full, 4, sa.SortRule.LargestMagn)).max() <= 1e-9
+    assert e.eigenvectors(2).shape == (n, 2)
+
+
+def test_complex_mband_million_rows(ctx):
+    n, k, m = 1_000_000, 10, 30
+    L = workloads.herm_band(n)
+    op = sa.SparseHermMatProd(L, "L", ctx)
+    assert op.nnz() == 2 * L.nnz - n
+    eigs = sa.HermEigsSolver(op, k, m)
+    eigs.init()
+    assert eigs.compute(sa.SortRule.LargestMagn) == k and eigs.info() == sa.CompInfo.Successful
+    evals, U = eigs.eigenvalues(), eigs.eigenvectors()
+    full = (L + sp.tril(L, -1).conj().T).tocsr()
+    assert np.abs(full @ U - U * evals).max() <= 1e-9
+    assert np.abs(U.conj().T @ U - np.eye(k)).max() <= 1e-10

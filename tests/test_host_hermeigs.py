@@ -1,0 +1,102 @@
+"""CPU-side checks of the complex Hermitian eigensolver (HermEigsSolver<...<std::complex<double>>>): the restart primitives of the
+complex factorisation's control flow (spectra_amd/csrc/zfac_flow.hpp: set_H, compress_real, ritz_vectors) on a host backend against
+numpy (tests/herm_checks.py; the GPU runs the same checks in tests/test_gpu_zcsr.py), the new C-ABI symbols, and that the
+reference's own test/HermEigs.cpp compiles against include/Spectra."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import herm_checks as HC
+import zfac_checks as Z
+from spectra_amd import _capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REFERENCE = os.environ.get("MISPEC_REFERENCE_DIR", "/root/reference")
+
+NEW_SYMBOLS = ["mispec_zcsr_upload", "mispec_zcsr_destroy", "mispec_zcsr_rows", "mispec_zcsr_cols", "mispec_zcsr_nnz",
+               "mispec_zcsr_spmv_host", "mispec_zcsr_coeff", "mispec_zcsr_spmv_time", "mispec_zfac_create_csr", "mispec_zfac_set_H",
+               "mispec_zfac_compress_real", "mispec_zfac_ritz_vectors", "mispec_zfac_kernel_time", "mispec_hermeigs_create_csr", "mispec_hermeigs_create_dense",
+               "mispec_hermeigs_destroy", "mispec_hermeigs_init", "mispec_hermeigs_compute", "mispec_hermeigs_info",
+               "mispec_hermeigs_num_iterations", "mispec_hermeigs_num_operations", "mispec_hermeigs_eigenvalues",
+               "mispec_hermeigs_eigenvectors"]
+
+
+def test_new_symbols_resolve_in_the_extras_library():
+    import spectra_amd as sa
+
+    lib = sa.lib()
+    extras = C.CDLL(_capi.EXTRAS_LIB_PATH)
+    for nm in NEW_SYMBOLS:
+        assert hasattr(lib, nm), nm
+        assert hasattr(extras, nm), nm
+        assert nm.startswith(_capi.EXTRAS_PREFIXES), nm
+        assert nm in _capi.SIGNATURES, nm
+
+
+@pytest.fixture(scope="module")
+def hostlib(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("zrestart") / "libzfac_restart_host.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-shared", "-fPIC", "-I" + os.path.join(ROOT, "spectra_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "zfac_restart_host_capi.cpp"), "-o", so])
+    lib = C.CDLL(so)
+    i64, vp = C.c_int64, C.c_void_p
+    dp, vpp = C.POINTER(C.c_double), C.POINTER(C.c_void_p)
+    lib.mispec_zdense_upload.argtypes = [vp, i64, i64, dp, i64, C.c_int, C.c_char, vpp]
+    lib.mispec_zfac_create_dense.argtypes = [vp, vp, C.c_int, C.c_int, vpp]
+    for nm in ("mispec_zdense_destroy", "mispec_zfac_destroy", "mispec_zfac_subspace_dim"):
+        getattr(lib, nm).argtypes = [vp]
+    lib.mispec_zfac_init.argtypes = [vp, dp, C.POINTER(i64)]
+    lib.mispec_zfac_factorize.argtypes = [vp, C.c_int, C.c_int, C.POINTER(i64)]
+    lib.mispec_zfac_f_norm.argtypes = [vp, dp]
+    lib.mispec_zfac_get_H.argtypes = [vp, dp]
+    lib.mispec_zfac_get_V.argtypes = [vp, C.c_int, dp]
+    lib.mispec_zfac_get_f.argtypes = [vp, dp]
+    lib.mispec_zfac_set_H.argtypes = [vp, dp]
+    lib.mispec_zfac_compress_real.argtypes = [vp, dp, C.c_int]
+    lib.mispec_zfac_ritz_vectors.argtypes = [vp, dp, C.c_int, dp]
+    return lib
+
+
+@pytest.mark.parametrize("n,m,k", [(12, 6, 3), (200, 30, 12), (500, 40, 20)])
+def test_hermitian_restart_flow_on_a_host_backend(hostlib, n, m, k):
+    A = Z.matrix(n, True, seed=n)
+    D, fac = C.c_void_p(), C.c_void_p()
+    Z.ok(hostlib.mispec_zdense_upload(None, n, n, Z.dp(A), n, 0, b"L", C.byref(D)))
+    Z.ok(hostlib.mispec_zfac_create_dense(None, D, m, 1, C.byref(fac)))
+    try:
+        HC.restart_checks(hostlib, fac, A, m, k)
+    finally:
+        hostlib.mispec_zfac_destroy(fac)
+        hostlib.mispec_zdense_destroy(D)
+
+
+def test_compress_rejects_a_partial_factorisation(hostlib):
+    n, m = 20, 8
+    A = Z.matrix(n, True, seed=1)
+    D, fac = C.c_void_p(), C.c_void_p()
+    Z.ok(hostlib.mispec_zdense_upload(None, n, n, Z.dp(A), n, 0, b"L", C.byref(D)))
+    Z.ok(hostlib.mispec_zfac_create_dense(None, D, m, 1, C.byref(fac)))
+    try:
+        v0 = np.ones(n, dtype=np.complex128)
+        cnt = C.c_int64(0)
+        Z.ok(hostlib.mispec_zfac_init(fac, Z.dp(v0), C.byref(cnt)))
+        Q = np.asfortranarray(np.eye(m))
+        assert hostlib.mispec_zfac_compress_real(fac, Z.dp(Q), 3) == Z.MISPEC_EINVAL
+    finally:
+        hostlib.mispec_zfac_destroy(fac)
+        hostlib.mispec_zdense_destroy(D)
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "test")), reason="the reference's sources are not on this machine")
+def test_reference_hermeigs_program_compiles(tmp_path):
+    """test/HermEigs.cpp, unmodified, against include/Spectra with tests/cpp/eigen_lite (+ eigen_lite_herm) in Eigen's place (the
+    flags of oracle/build_ref_programs.sh, as __graft_entry__.build_reference_test_programs runs it)."""
+    obj = str(tmp_path / "HermEigs.o")
+    subprocess.check_call(["g++", "-std=c++11", "-O0", "-w", "-I" + os.path.join(ROOT, "tests", "cpp", "eigen_lite_herm"),
+                           "-I" + os.path.join(ROOT, "tests", "cpp", "eigen_lite"),
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(REFERENCE, "test"),
+                           "-c", os.path.join(REFERENCE, "test", "HermEigs.cpp"), "-o", obj])
+    assert os.path.getsize(obj) > 0
