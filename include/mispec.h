@@ -45,23 +45,33 @@ const char* mispec_last_error(void);
 /* "x.y.z (gfx950)" */
 const char* mispec_version(void);
 
-/* Tuning switches and test hooks, by name (value NULL: back to the default).  The library reads no other global state; a name that
- * has not been set falls back to the environment variable MISPEC_<NAME IN UPPER CASE> — the test-only override the A/B tools
- * and the parity tests use.  Unknown names: MISPEC_EINVAL.  Names and values:
+/* Tuning switches and test hooks, by name (value NULL: back to the default).  The library reads no other global state; an option
+ * that has not been set falls back to the environment variable MISPEC_<NAME IN UPPER CASE> (empty: unset) — the test-only
+ * override the A/B tools and the parity tests use.  An unknown name or a value the option does not accept: MISPEC_EINVAL, the
+ * message lists the accepted values.  A value from the environment is checked when the library reads it: the call that reads it
+ * fails with MISPEC_EINVAL naming the variable.  Names and values:
  *   orth            onesweep (default) | onesweep-eager | reference      control flow of the Lanczos steps at creation
  *   one_reduction   1 (default) | 0                                      one reduction per one-sweep step
- *   orth_kernel     dma (default, >= 131072 rows) | dma2 | dmac | dmap | reg   the one-sweep pass: LDS-DMA ring or registers
+ *   orth_kernel     dma | dma2 | reg                                     the orthogonalisation passes: LDS-DMA ring of three / two slots,
+ *                                                                        or registers (unset: dma from 131072 rows on, else reg)
  *   host_turn       fast (default) | copy                                restart's host turn: pinned-memory kernels or hipMemcpy
  *   small           host (default) | host-serial | device                where the ncv x ncv work of a restart runs (host: the shifted
  *                                                                        QR sweeps as a skewed pipeline; host-serial: in the reference's order, same bits)
  *   restart_sync    0 (default) | 1                                      synchronising fused restart
  *   host_steps      0 (default) | 1                                      host-synchronous steps
- *   spec_corr       corrections enqueued speculatively per step (reference flow)
- *   overlap, exchange                                                    sharded product: 0 switches the overlap / the neighbour exchange off
- *   csr_win, csr_win_iters, csr_win_pf, csr_win_nt, dia2, spmv_tiles, spmv_staged, reorder, kernel_probe   SpMV format / kernel choice
- *   host_threads    upper bound on the host threads of the ingest / the shift solve's host-side factorisation (tests: results do not depend on it)
- *   vq              mfma: the f64-MFMA variant of V*Q
- *   shift           banded shift solve: key=value list — kernel variants that must agree (tests) and profile=1 (set_shift's phases on stderr)
+ *   spec_corr       1 ... 4 (unset: 2, 1 when sharded)                   corrections enqueued speculatively per step
+ *   overlap         1 (default) | 0                                      sharded product: overlap of the exchange with the local rows
+ *   exchange        allgather | halo (unset: halo when the halos are small) sharded product: all-gather or neighbour exchange
+ *   csr_win         1 (default) | 0                                      x windows of the int32 CSR kernel
+ *   reorder         auto (default) | rcm | none                          reverse Cuthill-McKee at ingest / in the shift solve
+ *   spmv_staged, spmv_tiles   auto (default) | 0 | 1                     staged / tile format for scattered patterns: never / always
+ *   host_threads    integer >= 1                                         upper bound on the host threads of the ingest / the shift solve's
+ *                                                                        host-side factorisation (tests: results do not depend on it)
+ *   shift           comma list of lds=0|1, batch=8|16|32, lanes=8|16|32|64, block_inverse=<MiB>, factor=host|device, wave=0|1,
+ *                   profile=0|1, each key at most once — banded shift solve: kernel variants that must agree (tests), set_shift's
+ *                   phases on stderr
+ * mispec_get_option returns the value in effect (the one set, else the environment's; not checked), NULL when there is none or
+ * the name is unknown, in a buffer of the calling thread that stays valid until that thread calls mispec_get_option again.
  * The reference has no counterpart (its only switches are template parameters). */
 int mispec_set_option(const char* name, const char* value);
 const char* mispec_get_option(const char* name);
@@ -220,7 +230,9 @@ int mispec_csr_staged_info(const mispec_csr* A, int64_t* bins, int64_t* slots, i
  * storage) incl. the H2D copies of the CSR arrays, [4] far-gather statistics + reordering, [5] tile image on the host, [6] its
  * upload and split, [8] staged image on the host, [9] its upload.  count <= 10 values are written. */
 int mispec_last_ingest_info(double* seconds_out, int count);
-int mispec_ingest_threads(void); /* host threads the ingest stages use: the machine's hardware threads, at most 64 */
+/* host threads the ingest stages use: the machine's hardware threads, at most 64 and at most option host_threads; < 0: error
+ * (an invalid MISPEC_HOST_THREADS) */
+int mispec_ingest_threads(void);
 /* Host-only test hook (no device needed): the full symmetric CSR matrix (rows sorted by column) that mispec_csr_from_triangle
  * derives from one stored triangle — built by the library's host threads, the same bytes whatever their number.  rowptr_out has
  * n + 1 entries, colind_out / val_out `capacity` entries (twice the input's entries always suffice); *nnz_out = entries written. */

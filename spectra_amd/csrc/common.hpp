@@ -137,13 +137,47 @@ struct PinnedBuf
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
-// Tuning switches and test hooks: ONE table, set through mispec_set_option(name, value) (include/mispec.h lists the names).
-// A name that has not been set falls back to the environment variable MISPEC_<NAME IN UPPER CASE> — kept as the test-only
-// override of the A/B tools and the parity tests (VERDICT r05 hygiene item: no getenv() scattered through the kernels' files).
-// Returns nullptr when neither is present.  The pointer stays valid until the option is set again.
-const char* option(const char* name);
-int option_int(const char* name, int dflt);
-bool option_is(const char* name, const char* value);
+// Tuning switches and test hooks: ONE table (ctx.hip; include/mispec.h lists names and values), set through
+// mispec_set_option(name, value).  An option that has not been set falls back to its environment variable MISPEC_<NAME> — the
+// test-only override of the A/B tools and the parity tests (nothing else reads the environment); an empty variable counts as unset.
+// Every read checks the value against the option's entry and throws Error(MISPEC_EINVAL) for one it does not accept, so an entry
+// point that reads an option runs inside guarded().  Reads return values, never pointers into the table.
+enum class Opt
+{
+    orth, one_reduction, orth_kernel, host_turn, small, restart_sync, host_steps, overlap, csr_win, spec_corr, exchange, reorder,
+    spmv_staged, spmv_tiles, host_threads, shift, count
+};
+// the values of the choice options, in the order of their entries' lists (`unset` is no value: the option not given)
+enum class Orth { onesweep, onesweep_eager, reference };
+enum class OrthKernel { dma, dma2, reg, unset };
+enum class HostTurn { fast, copy };
+enum class Small { host, host_serial, device };
+enum class Exchange { allgather, halo, unset };
+enum class Reorder { automatic, rcm, none };
+enum class Tri { automatic, off, on };  // auto | 0 | 1
+// choice option: its value as the enum above, `unset` when it is neither set nor in the environment
+int option_choice(Opt o);  // the index of the value in the entry's list, -1 when unset
+template <typename E>
+E option_choice(Opt o, E unset)
+{
+    const int i = option_choice(o);
+    return i < 0 ? unset : E(i);
+}
+bool option_flag(Opt o, bool unset);  // options of the values 0 | 1
+int option_int(Opt o, int unset);     // integer options: the value, within the entry's range
+// option shift: the key=value list of the banded shift solve's kernel variants, which tests require to agree (shiftsolve.hip), parsed;
+// a key that is absent keeps its default.  Not a tuning interface: the defaults are the measured best.
+struct ShiftOptions
+{
+    int lds = 1;              // 0: the general sweep kernel for every plain solve
+    int batch = 0;            // 8 | 16 | 32 rows per batch of the staged sweeps (0: by half-bandwidth)
+    int lanes = 0;            // 8 | 16 | 32 | 64 chunks per wavefront of the solve kernels (0: the default)
+    int block_inverse = 256;  // MiB per level for the explicit chunk inverses (0: sweeps everywhere)
+    int factor_host = 0;      // factor=host | device: the top level factored on the host / by k_chunk_factor
+    int wave = 1;             // 0: the lane-per-chunk kernels for the host-factored wide levels
+    int profile = 0;          // 1: set_shift's phases on stderr
+};
+ShiftOptions shift_options();
 
 // malloc for the gigabyte-sized host arrays of the ingest stages (free with std::free).  Throws std::bad_alloc.
 void* big_host_alloc(size_t bytes);

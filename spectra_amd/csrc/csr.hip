@@ -550,11 +550,10 @@ mispec_csr* upload_rows(mispec_ctx* ctx, int64_t n_rows, int64_t n_cols, const i
         // at ingest when reverse Cuthill-McKee localises them (reorder.hip)
         // MISPEC_SPMV_TILES = auto (default) | 0 | 1: the column-blocked tile format for scattered patterns that stay
         // scattered (decided below, after the reordering attempt)
-        const char* tmode = option("spmv_tiles");
-        const bool tiles_off = tmode && std::strcmp(tmode, "0") == 0, tiles_force = tmode && std::strcmp(tmode, "1") == 0;
-        const char* mode = option("reorder");
-        const bool off = mode && std::strcmp(mode, "none") == 0;
-        const bool force = mode && std::strcmp(mode, "rcm") == 0;
+        const Tri tiles = option_choice(Opt::spmv_tiles, Tri::automatic);
+        const bool tiles_off = tiles == Tri::off, tiles_force = tiles == Tri::on;
+        const Reorder reorder = option_choice(Opt::reorder, Reorder::automatic);
+        const bool off = reorder == Reorder::none, force = reorder == Reorder::rcm;
         if (allow_reorder && !off && ctx->world() == 1 && ctx->comm.allgather == nullptr && n_rows == n_cols && p1 > p0)
         {
             IngestTimer timer(4);
@@ -573,8 +572,8 @@ mispec_csr* upload_rows(mispec_ctx* ctx, int64_t n_rows, int64_t n_cols, const i
             // MISPEC_SPMV_STAGED = auto (default) | 0 | 1: the two-phase format with x and y in LDS (staged.hip).  Since round 4 it is
             // what scattered patterns get (M-rand n = 1e7 in the solver loop: 1.02 ms against 1.45 ms from the tiles); the tiles
             // are then built only on request (MISPEC_SPMV_TILES=1) or when the staged format declines the matrix.
-            const char* smode = option("spmv_staged");
-            const bool st_off = smode && std::strcmp(smode, "0") == 0, st_force = smode && std::strcmp(smode, "1") == 0;
+            const Tri staged = option_choice(Opt::spmv_staged, Tri::automatic);
+            const bool st_off = staged == Tri::off, st_force = staged == Tri::on;
             const bool scattered = n_cols >= 2 * kFarWindow && far > 0.25;
             bool staged_built = false;
             if (!st_off && (st_force || scattered))
@@ -940,7 +939,12 @@ extern "C" int mispec_csr_upload(mispec_ctx* ctx, int64_t n_rows, int64_t n_cols
     });
 }
 
-extern "C" int mispec_ingest_threads(void) { return mispec::ingest_threads(); }
+extern "C" int mispec_ingest_threads(void)
+{
+    int n = 0;
+    const int rc = guarded([&] { n = mispec::ingest_threads(); });
+    return rc == MISPEC_OK ? n : rc;
+}
 
 extern "C" int mispec_last_ingest_info(double* seconds_out, int count)
 {

@@ -548,10 +548,8 @@ void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
     double* y_dev = L.y_dev;
         const DiaArgs da{A.dia.p, A.dia_off.p, A.dia_ld, A.ndia, int(A.n_cols - 1), A.row_begin};
         // x staged through LDS windows when the offsets form at most 8 clusters, else direct loads (k_spmv_dia)
-        // two rows per thread with 16-byte loads (k_spmv_dia_win2) when the layout and the alignment allow; MISPEC_DIA2=0: the
-        // one-row-per-thread kernel
-        const bool dia2_off = option_int("dia2", 1) == 0;
-        const bool dia2 = !dia2_off && A.dia_win.nc > 0 && A.dia_ld == 0 && A.ndia <= 2 * kDiaGroup &&
+        // two rows per thread with 16-byte loads (k_spmv_dia_win2) when the layout and the alignment allow
+        const bool dia2 = A.dia_win.nc > 0 && A.dia_ld == 0 && A.ndia <= 2 * kDiaGroup &&
                           (reinterpret_cast<uintptr_t>(y_dev) & 15) == 0 &&
                           (!epi || ((reinterpret_cast<uintptr_t>(e.v_rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(e.v_prev) & 15) == 0));
         if (dia2)

@@ -6,7 +6,6 @@
 #include "csr_kernels.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <vector>
@@ -312,7 +311,7 @@ void build_windows_host(int64_t nrows, int64_t n_cols, int64_t row_begin, const 
 
 // XI: 16-byte window loads per thread (windows of at most 512 * XI doubles); PF: the next chunk's val / col_ind loads are
 // issued before the current chunk's products (two chunks of registers).
-template <bool EPI, int ITERS, int XI, bool PF, bool NT = false>
+template <bool EPI, int ITERS, int XI, bool PF>
 __global__ __launch_bounds__(256) void k_spmv_csr_win(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                       const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y,
                                                       int64_t nrows, int nblocks, SpmvEpilogue epi, const int32_t* __restrict__ wtab,
@@ -381,21 +380,9 @@ __global__ __launch_bounds__(256) void k_spmv_csr_win(const int32_t* __restrict_
         for (int it = 0; it < ITERS; it++)
         {
             const int base = min(a0 + tid * 4 + it * (kThreads * 4), last);
-            if (NT)  // the matrix stream is read once: keep it from evicting the x windows the XCD's blocks share in L2
-            {
-                const v2d a01 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(val + base));
-                const v2d a23 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(val + base + 2));
-                const v4i c4 = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(colind + base));
-                C.va[it][0] = make_double2(a01.x, a01.y);
-                C.va[it][1] = make_double2(a23.x, a23.y);
-                C.ci[it] = make_int4(c4.x, c4.y, c4.z, c4.w);
-            }
-            else
-            {
-                C.va[it][0] = *reinterpret_cast<const double2*>(val + base);
-                C.va[it][1] = *reinterpret_cast<const double2*>(val + base + 2);
-                C.ci[it] = *reinterpret_cast<const int4*>(colind + base);
-            }
+            C.va[it][0] = *reinterpret_cast<const double2*>(val + base);
+            C.va[it][1] = *reinterpret_cast<const double2*>(val + base + 2);
+            C.ci[it] = *reinterpret_cast<const int4*>(colind + base);
         }
     };
     Chunk cur, nxt;
@@ -554,7 +541,7 @@ namespace mispec {
 // the entries get their x from a window; MISPEC_CSR_WIN=0 keeps k_spmv_csr_stream for every matrix.
 void build_windows(mispec_csr& A)
 {
-    const bool off = option_is("csr_win", "0");
+    const bool off = !option_flag(Opt::csr_win, true);
     const int64_t nloc = A.local_rows();
     // (columns at or beyond the start sentinel of unused windows would select a padding window: no table for such a matrix — ADVICE r05)
     if (off || nloc == 0 || A.nnz == 0 || spmv_rows_per_block() != 256 || A.n_cols > int64_t(kWinPad))
@@ -599,54 +586,27 @@ void launch_spmv_csr_win(const mispec_csr& A, const SpmvLaunch& L)
     const hipEvent_t ev_start = L.ev_start, ev_stop = L.ev_stop;
     const double* x_dev = L.x_dev;
     double* y_dev = L.y_dev;
-        // MISPEC_CSR_WIN_ITERS = 2 | 4 (chunk of 2032 / 4080 products), MISPEC_CSR_WIN_PF = 0 | 1 (next chunk's loads ahead)
-        // (read once; MISPEC_KERNEL_PROBE=1 — tools/probe_csr_win.py — re-reads them at every launch so that one process can compare)
-        struct Knobs
-        {
-            int iters, pf;
-            bool nt;
-        };
-        const auto read_knobs = [] {
-            const char* e_iters = option("csr_win_iters");
-            const char* e_pf = option("csr_win_pf");
-            const char* e_nt = option("csr_win_nt");
-            return Knobs{e_iters ? atoi(e_iters) : 0, e_pf ? atoi(e_pf) : -1, e_nt && atoi(e_nt) != 0};
-        };
-        const bool probe = option("kernel_probe") != nullptr;
-        static const Knobs cached = read_knobs();
-        const Knobs knobs = probe ? read_knobs() : cached;
-        const int env_iters = knobs.iters, env_pf = knobs.pf;
-        const bool nt = knobs.nt;
         // measured in the solver loop (profiles/r09a, r09b): chunks of 1008 products with the next chunk's loads ahead — the
         // smallest LDS footprint, most resident blocks — for up to 16 entries per row (M-band 0.372 -> 0.369 ms, jittered band
-        // 0.412 -> 0.368 ms against the gather kernel on the same box); longer rows take larger chunks (fewer barrier rounds)
-        const int auto_iters = double(A.nnz) <= 16.0 * double(nloc) ? 1 : (double(A.nnz) <= 32.0 * double(nloc) ? 2 : 4);
-        int iters = env_iters == 1 || env_iters == 2 || env_iters == 4 ? env_iters : auto_iters;
+        // 0.412 -> 0.368 ms against the gather kernel on the same box); longer rows take larger chunks (fewer barrier rounds):
+        // 2032 products with the loads ahead, 4080 without (two chunks of registers would not fit)
+        int iters = double(A.nnz) <= 16.0 * double(nloc) ? 1 : (double(A.nnz) <= 32.0 * double(nloc) ? 2 : 4);
         // (64 bytes of margin: the kernel's static `red[4]` shares the 64 KiB with the dynamic allocation — ADVICE r05)
         while (iters > 1 && size_t(chunk_cap(256) - (4 - iters) * 1024 + 4 + A.win_lds_doubles) * sizeof(double) > 65536 - 64)
             iters >>= 1;  // products + windows within the 64 KiB a launch gets without an attribute
-        const bool pf = env_pf >= 0 ? env_pf != 0 : true;
         const int xi = (A.win_lds_doubles + 511) / 512;
         const int cap = chunk_cap(256) - (4 - iters) * 1024;
         const size_t lds = size_t(cap + 4 + A.win_lds_doubles) * sizeof(double);
         const int col_max = int(A.n_cols - 1);
-#define MISPEC_WIN_LAUNCH_NT(E, I, X, P, N)                                                                                           \
+#define MISPEC_WIN_LAUNCH(E, I, X, P)                                                                                             \
     do                                                                                                                             \
     {                                                                                                                              \
         if (ev_start && ev_stop)                                                                                                   \
-            hipExtLaunchKernelGGL((k_spmv_csr_win<E, I, X, P, N>), grid, block, lds, A.ctx->stream, ev_start, ev_stop, 0, A.rowptr.p, \
+            hipExtLaunchKernelGGL((k_spmv_csr_win<E, I, X, P>), grid, block, lds, A.ctx->stream, ev_start, ev_stop, 0, A.rowptr.p,  \
                                   A.colind.p, A.val.p, x_dev, y_dev, nloc, nblocks, e, A.wtab.p, col_max);                          \
         else                                                                                                                       \
-            hipLaunchKernelGGL((k_spmv_csr_win<E, I, X, P, N>), grid, block, lds, A.ctx->stream, A.rowptr.p, A.colind.p, A.val.p,  \
+            hipLaunchKernelGGL((k_spmv_csr_win<E, I, X, P>), grid, block, lds, A.ctx->stream, A.rowptr.p, A.colind.p, A.val.p,     \
                                x_dev, y_dev, nloc, nblocks, e, A.wtab.p, col_max);                                                 \
-    } while (0)
-#define MISPEC_WIN_LAUNCH(E, I, X, P)               \
-    do                                              \
-    {                                               \
-        if (nt)                                     \
-            MISPEC_WIN_LAUNCH_NT(E, I, X, P, true); \
-        else                                        \
-            MISPEC_WIN_LAUNCH_NT(E, I, X, P, false); \
     } while (0)
 #define MISPEC_WIN_X(E, I, P)              \
     do                                     \
@@ -660,19 +620,15 @@ void launch_spmv_csr_win(const mispec_csr& A, const SpmvLaunch& L)
         else                               \
             MISPEC_WIN_LAUNCH(E, I, 12, P); \
     } while (0)
-#define MISPEC_WIN(E)                     \
-    do                                    \
-    {                                     \
-        if (iters == 2 && pf)             \
-            MISPEC_WIN_X(E, 2, true);     \
-        else if (iters == 2)              \
-            MISPEC_WIN_X(E, 2, false);    \
-        else if (iters == 1 && pf)        \
-            MISPEC_WIN_X(E, 1, true);     \
-        else if (iters == 1)              \
-            MISPEC_WIN_X(E, 1, false);    \
-        else                              \
-            MISPEC_WIN_X(E, 4, false);    \
+#define MISPEC_WIN(E)                 \
+    do                                \
+    {                                 \
+        if (iters == 1)               \
+            MISPEC_WIN_X(E, 1, true); \
+        else if (iters == 2)          \
+            MISPEC_WIN_X(E, 2, true); \
+        else                          \
+            MISPEC_WIN_X(E, 4, false); \
     } while (0)
         if (epi)
             MISPEC_WIN(true);
@@ -681,7 +637,6 @@ void launch_spmv_csr_win(const mispec_csr& A, const SpmvLaunch& L)
 #undef MISPEC_WIN
 #undef MISPEC_WIN_X
 #undef MISPEC_WIN_LAUNCH
-#undef MISPEC_WIN_LAUNCH_NT
         MISPEC_HIP(hipGetLastError());
         return;
 }

@@ -13,7 +13,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <cctype>
 #include <condition_variable>
 #include <exception>
 #include <thread>
@@ -36,48 +35,230 @@ void* big_host_alloc(size_t bytes)
 
 // ---- options (common.hpp) ----------------------------------------------------------------------------------------------
 namespace {
-struct OptionTable
+enum class Kind { choice, integer, shift };
+struct OptionEntry
+{
+    Opt id;
+    const char* name;
+    const char* env;          // read when the option has not been set
+    Kind kind;
+    const char* values[4];    // choice: the accepted values, in the order of the option's enum in common.hpp
+    int lo, hi;               // integer: the accepted range
+    const char* meaning;
+};
+constexpr int kMaxInt = 0x7fffffff;
+constexpr OptionEntry kOptions[] = {
+    {Opt::orth, "orth", "MISPEC_ORTH", Kind::choice, {"onesweep", "onesweep-eager", "reference"}, 0, 0,
+     "control flow of the Lanczos steps of the factorisations created afterwards"},
+    {Opt::one_reduction, "one_reduction", "MISPEC_ONE_REDUCTION", Kind::choice, {"0", "1"}, 0, 0,
+     "one reduction per one-sweep step (default 1)"},
+    {Opt::orth_kernel, "orth_kernel", "MISPEC_ORTH_KERNEL", Kind::choice, {"dma", "dma2", "reg"}, 0, 0,
+     "orthogonalisation passes through an LDS-DMA ring of three / two slots or through registers (unset: dma from 131072 rows)"},
+    {Opt::host_turn, "host_turn", "MISPEC_HOST_TURN", Kind::choice, {"fast", "copy"}, 0, 0,
+     "restart's host turn: pinned-memory kernels or hipMemcpy"},
+    {Opt::small, "small", "MISPEC_SMALL", Kind::choice, {"host", "host-serial", "device"}, 0, 0,
+     "where the ncv x ncv work of a restart runs"},
+    {Opt::restart_sync, "restart_sync", "MISPEC_RESTART_SYNC", Kind::choice, {"0", "1"}, 0, 0, "synchronising fused restart"},
+    {Opt::host_steps, "host_steps", "MISPEC_HOST_STEPS", Kind::choice, {"0", "1"}, 0, 0, "host-synchronous steps"},
+    {Opt::overlap, "overlap", "MISPEC_OVERLAP", Kind::choice, {"0", "1"}, 0, 0,
+     "sharded product: overlap of the exchange with the local rows (default 1)"},
+    {Opt::csr_win, "csr_win", "MISPEC_CSR_WIN", Kind::choice, {"0", "1"}, 0, 0, "x windows of the int32 CSR kernel (default 1)"},
+    {Opt::spec_corr, "spec_corr", "MISPEC_SPEC_CORR", Kind::integer, {}, 1, 4,
+     "corrections enqueued speculatively per step (unset: 2, 1 when sharded)"},
+    {Opt::exchange, "exchange", "MISPEC_EXCHANGE", Kind::choice, {"allgather", "halo"}, 0, 0,
+     "sharded product: the all-gather or the neighbour exchange (unset: the exchange when the halos are small)"},
+    {Opt::reorder, "reorder", "MISPEC_REORDER", Kind::choice, {"auto", "rcm", "none"}, 0, 0,
+     "reverse Cuthill-McKee ordering at ingest and of the shift solve"},
+    {Opt::spmv_staged, "spmv_staged", "MISPEC_SPMV_STAGED", Kind::choice, {"auto", "0", "1"}, 0, 0, "staged SpMV format"},
+    {Opt::spmv_tiles, "spmv_tiles", "MISPEC_SPMV_TILES", Kind::choice, {"auto", "0", "1"}, 0, 0, "column-blocked tile SpMV format"},
+    {Opt::host_threads, "host_threads", "MISPEC_HOST_THREADS", Kind::integer, {}, 1, kMaxInt,
+     "upper bound on the host threads of the ingest and of the shift solve's host-side factorisation"},
+    {Opt::shift, "shift", "MISPEC_SHIFT", Kind::shift, {}, 0, 0, "kernel variants of the banded shift solve"},
+};
+static_assert(sizeof(kOptions) / sizeof(kOptions[0]) == size_t(Opt::count), "one entry per option");
+constexpr bool entries_in_order()
+{
+    for (size_t i = 0; i < size_t(Opt::count); i++)
+        if (kOptions[i].id != Opt(i))
+            return false;
+    return true;
+}
+static_assert(entries_in_order(), "kOptions is indexed by Opt");
+
+// keys of option shift; a numeric value is stored as its number, any other as its index in the list (no list: an integer >= 0)
+struct ShiftKey
+{
+    const char* key;
+    const char* values[4];
+    int ShiftOptions::*field;
+};
+const ShiftKey kShiftKeys[] = {
+    {"lds", {"0", "1"}, &ShiftOptions::lds},
+    {"batch", {"8", "16", "32"}, &ShiftOptions::batch},
+    {"lanes", {"8", "16", "32", "64"}, &ShiftOptions::lanes},
+    {"block_inverse", {}, &ShiftOptions::block_inverse},
+    {"factor", {"device", "host"}, &ShiftOptions::factor_host},
+    {"wave", {"0", "1"}, &ShiftOptions::wave},
+    {"profile", {"0", "1"}, &ShiftOptions::profile},
+};
+
+struct OptionValues
 {
     std::mutex mu;
-    std::vector<std::pair<std::string, std::string>> set;  // few entries: a linear scan beats a map
-    // values handed out as const char*: a value that is replaced stays alive (the list only grows by what callers set)
-    std::vector<std::string*> retired;
+    bool set[size_t(Opt::count)] = {};
+    std::string value[size_t(Opt::count)];
 };
-OptionTable& option_table()
+OptionValues& option_values()
 {
-    static OptionTable* t = new OptionTable;  // never destroyed: option() may be called from static destructors
-    return *t;
+    static OptionValues* v = new OptionValues;  // never destroyed: options may be read from static destructors
+    return *v;
 }
-// every name the library reads (mispec_set_option rejects anything else, so that a typo cannot pass for a measurement)
-const char* const kOptionNames[] = {
-    "csr_win", "spmv_tiles", "reorder", "spmv_staged", "dia2", "csr_win_iters", "csr_win_pf", "csr_win_nt", "kernel_probe",
-    "overlap", "exchange", "small", "spec_corr", "one_reduction", "host_steps", "orth", "restart_sync", "vq", "shift",
-    "host_turn", "orth_kernel", "host_threads", nullptr};
+
+const OptionEntry* find_option(const char* name)
+{
+    for (const OptionEntry& e : kOptions)
+        if (std::strcmp(e.name, name) == 0)
+            return &e;
+    return nullptr;
+}
+
+// The effective value of option e into `out`: the one set, else its environment variable's.  Returns where it came from (for
+// messages), nullptr when there is none.
+const char* effective(const OptionEntry& e, std::string& out)
+{
+    OptionValues& v = option_values();
+    {
+        std::lock_guard<std::mutex> lock(v.mu);
+        if (v.set[size_t(e.id)])
+        {
+            out = v.value[size_t(e.id)];
+            return "mispec_set_option";
+        }
+    }
+    const char* env = std::getenv(e.env);
+    if (!env || !*env)
+        return nullptr;
+    out = env;
+    return e.env;
+}
+
+int index_of(const char* const (&values)[4], const std::string& v)
+{
+    for (int i = 0; i < 4 && values[i]; i++)
+        if (v == values[i])
+            return i;
+    return -1;
+}
+bool parse_int(const std::string& v, int lo, int hi, int& out)
+{
+    if (v.empty() || v.size() > 10)
+        return false;
+    long long x = 0;
+    for (const char c : v)
+    {
+        if (c < '0' || c > '9')
+            return false;
+        x = 10 * x + (c - '0');
+    }
+    out = int(x);
+    return x >= lo && x <= hi;
+}
+std::string join(const char* const (&values)[4], const char* sep)
+{
+    std::string s;
+    for (int i = 0; i < 4 && values[i]; i++)
+        s += std::string(i ? sep : "") + values[i];
+    return s;
+}
+
+[[noreturn]] void reject(const OptionEntry& e, const char* origin, const std::string& v)
+{
+    std::string accepted;
+    if (e.kind == Kind::choice)
+        accepted = join(e.values, " | ");
+    else if (e.kind == Kind::integer)
+        accepted = "an integer from " + std::to_string(e.lo) + (e.hi == kMaxInt ? " on" : " to " + std::to_string(e.hi));
+    else
+    {
+        accepted = "a comma list of";
+        for (const ShiftKey& k : kShiftKeys)
+            accepted += std::string(&k == kShiftKeys ? " " : ", ") + k.key + "=" +
+                        (k.values[0] ? join(k.values, "|") : "<integer from 0 on>");
+        accepted += ", each key at most once";
+    }
+    throw Error(MISPEC_EINVAL, std::string(origin) + ": '" + v + "' is not a value of option " + e.name + " (" + e.meaning +
+                                   "); accepted: " + accepted);
+}
+
+ShiftOptions parse_shift(const std::string& spec, const char* origin)
+{
+    ShiftOptions s;
+    unsigned seen = 0;
+    for (size_t pos = 0; pos <= spec.size();)
+    {
+        const size_t end = std::min(spec.find(',', pos), spec.size());
+        const std::string item = spec.substr(pos, end - pos);
+        const size_t eq = item.find('=');
+        const ShiftKey* key = nullptr;
+        for (const ShiftKey& k : kShiftKeys)
+            if (eq != std::string::npos && item.compare(0, eq, k.key) == 0)
+                key = &k;
+        const unsigned bit = key ? 1u << (key - kShiftKeys) : 0u;
+        const std::string v = key ? item.substr(eq + 1) : item;
+        int x = 0;
+        const int i = key ? index_of(key->values, v) : -1;
+        const bool number = parse_int(v, 0, kMaxInt, x);
+        if (!key || (seen & bit) || (key->values[0] ? i < 0 : !number))
+            reject(kOptions[size_t(Opt::shift)], origin, spec);
+        s.*key->field = number ? x : i;
+        seen |= bit;
+        pos = end + 1;
+    }
+    return s;
+}
+
+// the index of a choice option's value / an integer option's value; throws for a value the option does not accept
+int check(const OptionEntry& e, const std::string& v, const char* origin)
+{
+    int x = -1;
+    if (e.kind == Kind::shift)
+        parse_shift(v, origin);
+    else if (e.kind == Kind::choice ? (x = index_of(e.values, v)) < 0 : !parse_int(v, e.lo, e.hi, x))
+        reject(e, origin, v);
+    return x;
+}
+bool read(Opt o, int& x)
+{
+    const OptionEntry& e = kOptions[size_t(o)];
+    std::string v;
+    const char* origin = effective(e, v);
+    if (origin)
+        x = check(e, v, origin);
+    return origin != nullptr;
+}
 }  // namespace
 
-const char* option(const char* name)
+int option_choice(Opt o)
 {
-    OptionTable& t = option_table();
-    {
-        std::lock_guard<std::mutex> lock(t.mu);
-        for (auto& kv : t.set)
-            if (kv.first == name)
-                return kv.second.c_str();
-    }
-    std::string env = "MISPEC_";
-    for (const char* c = name; *c; c++)
-        env.push_back(char(std::toupper(static_cast<unsigned char>(*c))));
-    return std::getenv(env.c_str());
+    int x = -1;
+    return read(o, x) ? x : -1;
 }
-int option_int(const char* name, int dflt)
+bool option_flag(Opt o, bool unset)
 {
-    const char* v = option(name);
-    return v ? std::atoi(v) : dflt;
+    int x = 0;
+    return read(o, x) ? x != 0 : unset;
 }
-bool option_is(const char* name, const char* value)
+int option_int(Opt o, int unset)
 {
-    const char* v = option(name);
-    return v && std::strcmp(v, value) == 0;
+    int x = 0;
+    return read(o, x) ? x : unset;
+}
+ShiftOptions shift_options()
+{
+    const OptionEntry& e = kOptions[size_t(Opt::shift)];
+    std::string v;
+    const char* origin = effective(e, v);
+    return origin ? parse_shift(v, origin) : ShiftOptions{};
 }
 
 int ingest_threads()
@@ -88,8 +269,7 @@ int ingest_threads()
     }();
     // option host_threads (tests): an upper bound on the host threads of the ingest and of the shift solve's host-side
     // factorisation — their results must not depend on it
-    const int cap = option_int("host_threads", 0);
-    return cap >= 1 ? std::min(n, cap) : n;
+    return std::min(n, option_int(Opt::host_threads, n));
 }
 
 void parallel_ranges(int64_t n, int parts, const std::function<void(int, int64_t, int64_t)>& fn)
@@ -136,25 +316,30 @@ extern "C" int mispec_set_option(const char* name, const char* value)
 {
     return guarded([&] {
         MISPEC_REQUIRE(name != nullptr, "mispec_set_option: name is NULL");
-        bool known = false;
-        for (const char* const* k = kOptionNames; *k; k++)
-            known = known || std::strcmp(*k, name) == 0;
-        MISPEC_REQUIRE(known, std::string("mispec_set_option: unknown option '") + name + "'");
-        auto& t = option_table();
-        std::lock_guard<std::mutex> lock(t.mu);
-        for (size_t i = 0; i < t.set.size(); i++)
-            if (t.set[i].first == name)
-            {
-                t.retired.push_back(new std::string(std::move(t.set[i].second)));  // a pointer handed out earlier stays valid
-                t.set.erase(t.set.begin() + long(i));
-                break;
-            }
+        const OptionEntry* e = find_option(name);
+        MISPEC_REQUIRE(e, std::string("mispec_set_option: unknown option '") + name + "'");
         if (value)
-            t.set.emplace_back(name, value);
+            check(*e, value, "mispec_set_option");
+        OptionValues& v = option_values();
+        std::lock_guard<std::mutex> lock(v.mu);
+        v.set[size_t(e->id)] = value != nullptr;
+        v.value[size_t(e->id)] = value ? value : "";
     });
 }
 
-extern "C" const char* mispec_get_option(const char* name) { return name ? option(name) : nullptr; }
+// introspection: the effective string, not checked, in a copy of the calling thread's
+extern "C" const char* mispec_get_option(const char* name)
+{
+    static thread_local std::string copy;
+    const char* out = nullptr;
+    (void) guarded([&] {
+        const OptionEntry* e = name ? find_option(name) : nullptr;
+        MISPEC_REQUIRE(e, std::string("mispec_get_option: unknown option '") + (name ? name : "(null)") + "'");
+        if (effective(*e, copy))
+            out = copy.c_str();
+    });
+    return out;
+}
 
 extern "C" int mispec_ctx_create(int device, void* hip_stream, mispec_ctx** out)
 {

@@ -288,11 +288,7 @@ void sync_stream(mispec_fac& F)
 // option host_turn = fast | copy (default fast): how the state of a finished device-driven sweep reaches the host and how a restart's
 // Q reaches the device.  fast: kernels that write to / read from pinned host memory, the host spins on a sequence word (with
 // the stream's own status as the arbiter: an error or a completed stream without the word falls back to the copy).
-bool fast_host_turn()
-{
-    const char* v = option("host_turn");
-    return !v || std::string(v) != "copy";
-}
+bool fast_host_turn() { return option_choice(Opt::host_turn, HostTurn::fast) == HostTurn::fast; }
 
 // d_state -> *F.h_state, waited for.  One host synchronisation either way (n_sync counts it).
 void fetch_state(mispec_fac& F)
@@ -404,8 +400,7 @@ void plan_overlap(mispec_fac& F)
     F.interior_first = F.interior_count = 0;
     if (!F.A || !F.sharded() || F.ctx->world() < 2 || F.A2 || F.Bop || F.Chol || F.A->spmv_format() >= 3)  // tiles, staged: no row sub-ranges
         return;
-    const char* e = option("overlap");
-    if (e && atoi(e) == 0)
+    if (!option_flag(Opt::overlap, true))
         return;
     int first = 0, count = 0;
     interior_blocks(*F.A, F.row_begin, F.row_begin + F.nloc, first, count);
@@ -431,8 +426,8 @@ void plan_exchange(mispec_fac& F)
     const int W = cm.world, me = cm.rank;
     if (!F.A || !F.sharded() || !cm.exchange || W < 2)
         return;
-    const char* e = option("exchange");
-    if (e && std::string(e) == "allgather")
+    const Exchange mode = option_choice(Opt::exchange, Exchange::unset);
+    if (mode == Exchange::allgather)
         return;
     std::vector<int64_t> lo, hi;
     const bool have = column_ranges(*F.A, F.block, W, lo, hi);
@@ -470,7 +465,7 @@ void plan_exchange(mispec_fac& F)
         }
         worst = std::max(worst, total);
     }
-    const bool force = e && std::string(e) == "halo";
+    const bool force = mode == Exchange::halo;
     if (!force && 2 * worst > int64_t(W - 1) * F.block)
         return;  // the referenced parts are most of the vector: one all-gather is the better collective
     F.send_off.assign(size_t(W), 0);
@@ -979,11 +974,7 @@ void lanczos_corrections_host(mispec_fac& F, int i, int count)
 }
 
 // MISPEC_SMALL=device keeps the m x m work of a restart on the GPU (tested in both settings); the default is the host core.
-bool small_on_device()
-{
-    const bool on = option_is("small", "device");
-    return on;
-}
+bool small_on_device() { return option_choice(Opt::small, Small::host) == Small::device; }
 
 // One-sweep steps: apply the correction that the last step of the sweep left pending, then continue the reference's loop
 // (Lanczos.h:156-182) from "one correction applied".  H and beta already carry that correction (finish_lagged).
@@ -1089,10 +1080,7 @@ void lanczos_step_host(mispec_fac& F, int i, int64_t* nmatop)
 // launches on one device, but a real all-reduce per step when sharded — so it is left to the host path there.
 int speculative_corrections(const mispec_fac& F)
 {
-    const int knob = option_int("spec_corr", 0);
-    if (knob >= 1 && knob <= 4)
-        return knob;
-    return (F.sharded() && F.ctx->world() > 1) ? 1 : 2;
+    return option_int(Opt::spec_corr, (F.sharded() && F.ctx->world() > 1) ? 1 : 2);
 }
 void lanczos_step_device(mispec_fac& F, int i)
 {
@@ -1261,8 +1249,7 @@ void lanczos_step_lagged(mispec_fac& F, int i, bool last, bool defer)
 // MISPEC_ORTH_ONE_REDUCTION / MISPEC_ORTH_TWO_REDUCTIONS select it per factorisation)
 bool default_one_reduction()
 {
-    const char* e = option("one_reduction");
-    return e ? atoi(e) != 0 : true;  // the default since round 5 (C2: 0.986 -> 0.939 s per solve, same counters; profiles/r09l)
+    return option_flag(Opt::one_reduction, true);  // the default since round 5 (C2: 0.986 -> 0.939 s per solve, same counters; profiles/r09l)
 }
 
 bool device_operator(const mispec_fac& F) { return F.A != nullptr || (F.S != nullptr && F.Bcsr == nullptr) || F.D != nullptr || F.dop != nullptr; }
@@ -1840,16 +1827,13 @@ int fac_create_impl(mispec_ctx* ctx, const mispec_csr* A, const mispec_symshift*
             F->h_flag.alloc(8);
             F->h_flag.p[0] = 0;
             F->h_up.alloc(size_t(ncv) * ncv + 2 * size_t(ncv));
-            F->device_steps = option_int("host_steps", 0) == 0;
+            F->device_steps = !option_flag(Opt::host_steps, false);
             {
                 // default since round 4: the one-sweep steps (every gate of tests/test_gpu_onesweep.py and the reference's own test
                 // programs hold in both modes); MISPEC_ORTH=reference restores the reference's two-pass control flow everywhere
-                const char* o = option("orth");
-                const std::string mode = o ? o : "onesweep";
-                MISPEC_REQUIRE(mode == "onesweep" || mode == "reference" || mode == "onesweep-eager",
-                               "MISPEC_ORTH: expected reference, onesweep or onesweep-eager");
-                F->onesweep = mode != "reference";
-                F->eager_last = mode == "onesweep-eager";
+                const Orth mode = option_choice(Opt::orth, Orth::onesweep);
+                F->onesweep = mode != Orth::reference;
+                F->eager_last = mode == Orth::onesweep_eager;
                 F->onered = F->onesweep && default_one_reduction();
             }
             F->h_red.alloc(kPartialLd + 8);
@@ -2233,8 +2217,7 @@ extern "C" int mispec_fac_tridiag_eigen(mispec_fac* fac, double* evals_host, dou
         // host for the convergence test, so by default the m x m eigen-decomposition — a serial chain of rotations,
         // ~25 us on a host core against ~0.6 ms on one wavefront — runs where the data is.  MISPEC_SMALL=device
         // keeps it on the GPU (k_tridiag_eigen_w64 / k_tridiag_eigen; same routine, internal/SmallDense.h).
-        const bool on_device_env = option_is("small", "device");
-        const bool on_device = on_device_env && m <= kMaxSmallDim;
+        const bool on_device = small_on_device() && m <= kMaxSmallDim;
         if (!on_device)
         {
             F.counts[FAM_SMALL]++;
@@ -2278,8 +2261,7 @@ extern "C" int mispec_fac_ritz_values(mispec_fac* fac, double* evals_host, doubl
         mispec_fac& F = *fac;
         MISPEC_REQUIRE(F.symmetric, "mispec_fac_ritz_values: symmetric (Lanczos) factorisations only");
         const int m = F.m;
-        const bool on_device_env = option_is("small", "device");
-        if (on_device_env && m <= kMaxSmallDim)  // the device kernel forms the whole matrix: take its last row
+        if (small_on_device() && m <= kMaxSmallDim)  // the device kernel forms the whole matrix: take its last row
         {
             std::vector<double> U(size_t(m) * m);
             if (mispec_fac_tridiag_eigen(fac, evals_host, U.data()) != MISPEC_OK)
@@ -2376,7 +2358,7 @@ extern "C" int mispec_fac_restart_sym(mispec_fac* fac, const double* shifts_host
             // The sweeps as a skewed pipeline (internal/SmallDensePipelined.h): the serial order's T and Q bit for bit (the sweeps in
             // flight overlap on the out-of-order core, the rows of Q go through SIMD registers) in 40 % of its time — ~20 instead of
             // ~50 us at m = 40, 18 shifts, on the critical path of every restart.  Option small=host-serial: the reference's order.
-            if (option_is("small", "host-serial"))
+            if (option_choice(Opt::small, Small::host) == Small::host_serial)
             {
                 std::fill(Q, Q + size_t(m) * m, 0.0);
                 for (int i = 0; i < m; i++)
@@ -2405,7 +2387,7 @@ extern "C" int mispec_fac_restart_sym(mispec_fac* fac, const double* shifts_host
             // start state of the next sweep in d_state — H after compress_H is known here, beta = |f_new| follows from the
             // record —, so factorize_lanczos enqueues that sweep at once; should the corrected residual fail the reference's
             // test (Lanczos.h:156), none of its steps runs and the host continues the reference's loop at the sweep's end.
-            const bool no_sync = fused && !option_is("restart_sync", "1") && !F.test_recorrect && F.device_steps && device_operator(F) &&
+            const bool no_sync = fused && !option_flag(Opt::restart_sync, false) && !F.test_recorrect && F.device_steps && device_operator(F) &&
                                  !F.bmode();
             const bool fast = fast_host_turn();
             if (fast)

@@ -130,10 +130,11 @@ struct OrthArgs
     int onered = 0;
 };
 
-// ORTH_LAGGED with the basis streamed through an LDS ring by LDS-DMA (orth_dma.hip): eligible for one column panel on vectors of
-// at least 512 tiles of 128 rows; returns the number of partial records (= workgroups: one per CU).  depth_override 2: two ring slots.
+// ORTH_LAGGED with the basis streamed through an LDS ring by LDS-DMA (orth_dma.hip): eligible for one column panel, the default on
+// vectors of at least 1024 tiles of 128 rows (131072 rows, launch_orth_panel); returns the number of partial records (= workgroups:
+// one per CU).  depth_override 2: two ring slots.
 bool orth_lagged_dma_eligible(const OrthArgs& a);
-int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_override, int flags = 0);
+int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_override);
 
 // The other modes (reference flow, Arnoldi) the same way (orth_dma_modes.hip): one column panel, vectors of at least 1024 tiles.
 bool orth_dma_modes_eligible(OrthMode mode, const OrthArgs& a);

@@ -2,7 +2,7 @@
 // LDS-DMA (`global_load_lds_dwordx4`) instead of through registers — round 6, VERDICT r05 item 2.
 //
 // Why: the register version issues a tile's 20 x 16-byte loads per lane, waits for all of them, computes, and only then issues
-// the next tile's loads; its SQ / TCC counters (profiles/r11a_counters_c2_round5_tree.txt) show 90 128-byte requests in flight
+// the next tile's loads; its SQ / TCC counters (profiles/r11a_pmc_sq_tcc_tcp_onesweep_c2_round5_tree.txt) show 90 128-byte requests in flight
 // per CU on average at 1214 cycles per request — the memory system is asked for 5.8 TB/s, not saturated.  Holding a second
 // tile in flight costs 80 more VGPRs per lane in registers and nothing in LDS: here every wavefront keeps DEPTH - 1 tiles of its
 // own columns in flight (wave-private regions of a DEPTH-slot ring, 1 KiB per column and tile = one DMA instruction), waits
@@ -67,8 +67,8 @@ __device__ __forceinline__ void dma16(const double* gsrc, unsigned lds_dst)
                      : "memory");
 }
 
-template <int MAXS, int DEPTH, bool ONERED, bool NTV = true>
-__global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a, int contiguous)
+template <int MAXS, int DEPTH, bool ONERED>
+__global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a)
 {
     constexpr int NL = MAXS + 1;                  // DMA instructions per wavefront and tile: its columns + one of {f, src}
     constexpr int kRegion = kRows;                // doubles per (wave, column slot) region = 1 KiB
@@ -114,26 +114,23 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a, int
         const unsigned base = __builtin_amdgcn_readfirstlane(lds0 + unsigned((slot * kNW + w) * NL) * 1024u);
 #pragma unroll
         for (int jj = 0; jj < MAXS; jj++)
-            dma16<NTV>(colp[jj] + rc, base + unsigned(jj) * 1024u);
+            dma16<true>(colp[jj] + rc, base + unsigned(jj) * 1024u);
         dma16<false>(extra + rc, base + unsigned(MAXS) * 1024u);
     };
 
     // tiles of this workgroup: b, b + G, b + 2G, ... (neighbouring workgroups read neighbouring KiB of a column at about the same
-    // time) or, `contiguous`, one run of ceil(ntiles / G) tiles.  Below `t` is the tile id, advancing by `step`, ending at `tend`.
-    const int64_t per = (ntiles + G - 1) / G;
-    const int64_t step = contiguous ? 1 : G;
-    int64_t t = contiguous ? int64_t(blockIdx.x) * per : int64_t(blockIdx.x);
-    const int64_t tend = contiguous ? (t + per < ntiles ? t + per : ntiles) : ntiles;
-    if (t < tend)
+    // time; one contiguous run of tiles per workgroup measured slower, profiles/r11d)
+    int64_t t = blockIdx.x;
+    if (t < ntiles)
         issue(t, 0);
-    if (DEPTH == 3 && t + step < tend)
-        issue(t + step, 1);
+    if (DEPTH == 3 && t + G < ntiles)
+        issue(t + G, 1);
     int slot = 0, buf = 0;
     const int jp = a.ncol - 1;  // ONERED: column i-1 = slot jp / 4 of wavefront jp % 4 (a.ncol = i >= 1)
-    for (; t < tend; t += step)
+    for (; t < ntiles; t += G)
     {
         // ---- tile t of this wave's columns has landed ----
-        if (DEPTH == 3 && t + step < tend)
+        if (DEPTH == 3 && t + G < ntiles)
             asm volatile("s_waitcnt vmcnt(%0)" ::"i"(NL) : "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -156,11 +153,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a, int
         // ---- every wave has left tile t-1's slot: refill it (DEPTH 3: tile t+2G; DEPTH 2: tile t+G) ----
         if (DEPTH == 3)
         {
-            if (t + 2 * step < tend)
-                issue(t + 2 * step, slot == 0 ? 2 : slot - 1);
+            if (t + 2 * G < ntiles)
+                issue(t + 2 * G, slot == 0 ? 2 : slot - 1);
         }
-        else if (t + step < tend)
-            issue(t + step, slot ^ 1);
+        else if (t + G < ntiles)
+            issue(t + G, slot ^ 1);
         const int64_t r = t * kRows + 2 * lane;
         const bool valid = r < a.n;  // rows come in even pairs; vectors are zero-padded to an even length
         const double* tile = ring + slot * kSlotDoubles + 2 * lane;
@@ -246,39 +243,28 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a, int
     }
 }
 
-template <int MAXS, int DEPTH, bool ONERED, bool NTV>
-void launch_inst(const mispec_ctx& ctx, const OrthArgs& a, int grid, int contiguous)
+template <int MAXS, int DEPTH, bool ONERED>
+void launch_inst(const mispec_ctx& ctx, const OrthArgs& a, int grid)
 {
     const size_t lds = (size_t(DEPTH) * kNW * (MAXS + 1) * kRows + 2 * kNW * kRows + 64) * sizeof(double);
     // (the attribute is per device and function; one context per device and process in practice, and setting it again is harmless)
     static thread_local int attr_dev = -1;
     if (attr_dev != ctx.device)
     {
-        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_orth_lagged_dma<MAXS, DEPTH, ONERED, NTV>),
+        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_orth_lagged_dma<MAXS, DEPTH, ONERED>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
         attr_dev = ctx.device;
     }
-    hipLaunchKernelGGL((k_orth_lagged_dma<MAXS, DEPTH, ONERED, NTV>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx.stream, a,
-                       contiguous);
+    hipLaunchKernelGGL((k_orth_lagged_dma<MAXS, DEPTH, ONERED>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx.stream, a);
 }
 
-// flags: bit 0 contiguous tile runs per workgroup, bit 1 plain (not non-temporal) DMA loads of the basis — A/B switches
 template <int MAXS, int DEPTH>
-void launch_one(const mispec_ctx& ctx, const OrthArgs& a, int grid, int flags)
+void launch_one(const mispec_ctx& ctx, const OrthArgs& a, int grid)
 {
-    const int contiguous = flags & 1;
-    if (DEPTH == 3 && (flags & 2))
-    {
-        if (a.onered)
-            launch_inst<MAXS, DEPTH, true, DEPTH != 3>(ctx, a, grid, contiguous);
-        else
-            launch_inst<MAXS, DEPTH, false, DEPTH != 3>(ctx, a, grid, contiguous);
-        return;
-    }
     if (a.onered)
-        launch_inst<MAXS, DEPTH, true, true>(ctx, a, grid, contiguous);
+        launch_inst<MAXS, DEPTH, true>(ctx, a, grid);
     else
-        launch_inst<MAXS, DEPTH, false, true>(ctx, a, grid, contiguous);
+        launch_inst<MAXS, DEPTH, false>(ctx, a, grid);
 }
 
 }  // namespace
@@ -292,7 +278,7 @@ bool orth_lagged_dma_eligible(const OrthArgs& a)
     return a.ncol >= 1 && a.ncol < kPanelCols && slots <= 16 && a.n >= 1;
 }
 
-int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_override, int flags)
+int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_override)
 {
     const int64_t ntiles = (a.n + kRows - 1) / kRows;
     const int grid = int(std::min<int64_t>(ntiles, ctx.num_cu));  // one workgroup per CU (the ring does not leave room for two)
@@ -301,12 +287,12 @@ int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_o
     const bool three = slots <= 11 && depth_override != 2;
     switch (slots)
     {
-#define MISPEC_DMA_CASE(S)                       \
-    case S:                                      \
-        if (three)                               \
-            launch_one<S, 3>(ctx, a, grid, flags);      \
-        else                                     \
-            launch_one<S, 2>(ctx, a, grid, flags);      \
+#define MISPEC_DMA_CASE(S)                \
+    case S:                               \
+        if (three)                        \
+            launch_one<S, 3>(ctx, a, grid); \
+        else                              \
+            launch_one<S, 2>(ctx, a, grid); \
         break;
         MISPEC_DMA_CASE(1)
         MISPEC_DMA_CASE(2)
@@ -320,9 +306,9 @@ int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_o
         MISPEC_DMA_CASE(10)
         MISPEC_DMA_CASE(11)
 #undef MISPEC_DMA_CASE
-#define MISPEC_DMA_CASE2(S)                  \
-    case S:                                  \
-        launch_one<S, 2>(ctx, a, grid, flags);      \
+#define MISPEC_DMA_CASE2(S)             \
+    case S:                             \
+        launch_one<S, 2>(ctx, a, grid); \
         break;
         MISPEC_DMA_CASE2(12)
         MISPEC_DMA_CASE2(13)

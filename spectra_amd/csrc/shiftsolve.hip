@@ -1216,7 +1216,11 @@ struct PhaseTimer
     int b;
     bool on;
     std::chrono::steady_clock::time_point t0;
-    PhaseTimer(const char* w, int64_t n_, int b_);
+    PhaseTimer(const char* w, int64_t n_, int b_) : what(w), n(n_), b(b_), on(shift_options().profile != 0)
+    {
+        if (on)
+            t0 = std::chrono::steady_clock::now();
+    }
     ~PhaseTimer()
     {
         if (on)
@@ -1311,47 +1315,10 @@ void plan_level(int64_t N, int b, int64_t& L, int64_t& P)
     }
 }
 
-// MISPEC_SHIFT="key=value,...": ONE test hook for the kernel variants of the banded solve, so that tests can require that they
-// agree (tests/test_gpu_shift.py): lds=0 (always the general sweep kernel), batch=8|16|32 (rows per batch of the staged sweeps),
-// lanes=8|16|32|64 (chunks per wavefront), block_inverse=<MiB> (size limit of the explicit chunk inverses; 0: sweeps everywhere),
-// factor=host (the top level factored on the host).  Not a tuning interface: the defaults are the measured best.
-long long shift_option(const char* key, long long dflt)
-{
-    const char* spec_c = option("shift");
-    const std::string spec = spec_c ? spec_c : "";
-    const std::string k = std::string(key) + "=";
-    size_t pos = 0;
-    while (pos < spec.size())
-    {
-        size_t end = spec.find(',', pos);
-        if (end == std::string::npos)
-            end = spec.size();
-        if (spec.compare(pos, k.size(), k) == 0)
-        {
-            const std::string v = spec.substr(pos + k.size(), end - pos - k.size());
-            if (v == "host")
-                return 1;
-            if (v == "device")
-                return 0;
-            return atoll(v.c_str());
-        }
-        pos = end + 1;
-    }
-    return dflt;
-}
-
-}  // namespace
-PhaseTimer::PhaseTimer(const char* w, int64_t n_, int b_) : what(w), n(n_), b(b_), on(shift_option("profile", 0) != 0)
-{
-    if (on)
-        t0 = std::chrono::steady_clock::now();
-}
-namespace {
-
 // whether a level of this shape is factored by k_chunk_factor (MISPEC_SHIFT=factor=host keeps everything on the host)
 bool factored_on_device(int64_t N, int b)
 {
-    const bool host_only = shift_option("factor", 0) != 0;
+    const bool host_only = shift_options().factor_host != 0;
     int64_t L, P;
     plan_level(N, b, L, P);
     return P > 1 && b <= 8 && !host_only;
@@ -1362,7 +1329,7 @@ bool factored_on_device(int64_t N, int b)
 // (MISPEC_SHIFT=block_inverse=0 keeps the sweeps; =<MiB> moves the size limit, default 256 MiB per level).
 bool wants_block_inverse(int64_t P, int64_t mmax, int b)
 {
-    const long long limit_mib = shift_option("block_inverse", 256);
+    const long long limit_mib = shift_options().block_inverse;
     if (limit_mib <= 0 || mmax > 256 || b > 16)
         return false;
     const double bytes = double(P) * double(mmax) * double(mmax) * 8.0;
@@ -1408,7 +1375,7 @@ void factor_level(mispec_ctx* ctx, HostBand& M, BandLevel& lev, FactorStats& sta
     MISPEC_REQUIRE(on_device || !M.view, "internal: a band view is only valid for a level factored on the device");
     // host-factored levels of half-bandwidth 9...64 whose interiors get no explicit inverse: the row-major layout of the
     // wave-per-chunk solve (option shift=wave=0: the lane-per-chunk kernels of rounds 4-5 on the interleaved layout)
-    const bool wide = !on_device && b > 8 && P > 1 && shift_option("wave", 1) != 0 &&
+    const bool wide = !on_device && b > 8 && P > 1 && shift_options().wave != 0 &&
                       !(!stats.want_cholesky && wants_block_inverse(P, mmax, b));
     const ChunkStore cs = make_chunk_store(N, b, L, P, wide);
     lev.cs = cs;
@@ -1802,11 +1769,9 @@ void factor_level(mispec_ctx* ctx, HostBand& M, BandLevel& lev, FactorStats& sta
 // rows in flight during the recurrence) measured 0.281 against 0.265 ms (profiles/rounds_1_2/r03b_*) and was removed again.
 int solve_lanes(int64_t P)
 {
-    const int knob = int(shift_option("lanes", 0));
-    if (knob == 64 || knob == 32 || knob == 16 || knob == 8)
-        return knob;
+    const int knob = shift_options().lanes;
     (void) P;
-    return kChunkThreads;
+    return knob ? knob : kChunkThreads;
 }
 
 void launch_chunk_solve(const mispec_ctx& ctx, const BandLevel& lev, dim3 grid_unused, const double* f, double* y, int mode = 0,
@@ -1824,11 +1789,10 @@ void launch_chunk_solve(const mispec_ctx& ctx, const BandLevel& lev, dim3 grid_u
     const dim3 grid(unsigned((lev.P - 1 + lanes - 1) / lanes) + 1);  // + the last chunk's own workgroup
     const bool chol = mode != 0 || u_out != nullptr;
     // plain solves of a level whose wavefront segments fit the LDS: the staged kernel (MISPEC_SHIFT=lds=0: always the general one)
-    const bool lds_off = shift_option("lds", 1) == 0;
-    const int batch = int(shift_option("batch", 0));
-    if (!chol && !lds_off && lev.P > 1 && lev.b >= 1 && lev.b <= 8)
+    const ShiftOptions so = shift_options();
+    if (!chol && so.lds != 0 && lev.P > 1 && lev.b >= 1 && lev.b <= 8)
     {
-        const int U = (batch == 8 || batch == 16 || batch == 32) ? batch : (lev.b <= 4 ? 32 : 16);
+        const int U = so.batch ? so.batch : (lev.b <= 4 ? 32 : 16);
         const auto whole = [U](int64_t m) { return (m + U - 1) / U * U; };
         // LDS row stride of a chunk: the padded interior; the last chunk's (its workgroup holds it alone) may spread over all rows
         const int64_t ldl = std::max<int64_t>(whole(lev.L - lev.b), (whole(lev.N - (lev.P - 1) * lev.L) + lanes - 1) / lanes) | 1;
@@ -2305,7 +2269,7 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
         // (the adjacency below holds every off-diagonal entry of A and of B twice behind int32 row pointers: a pencil with more
         // entries than that is not reordered — it ends as the clean "unsupported pattern" error instead — ADVICE r05)
         if (!band_path(n, S->half_bandwidth) && n > kMaxDense && n < (int64_t(1) << 31) &&
-            2 * (countA + countB) < (int64_t(1) << 31) && !option_is("reorder", "none"))
+            2 * (countA + countB) < (int64_t(1) << 31) && option_choice(Opt::reorder, Reorder::automatic) != Reorder::none)
         {
             // Too wide for the band kernels as it comes and too large for the dense path: try a bandwidth-reducing ordering
             // (reverse Cuthill-McKee on the pattern of A (+ B)) before giving up — the reference's SparseLU / SimplicialLDLT

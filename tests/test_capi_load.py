@@ -114,3 +114,91 @@ def test_options_replace_the_environment_switches():
     finally:
         sa.set_option("spec_corr", None)
         del os.environ["MISPEC_SPEC_CORR"]
+
+
+# every value of the option table (include/mispec.h) with a meaning; each one is accepted and read back as set
+OPTION_VALUES = {
+    "orth": ["onesweep", "onesweep-eager", "reference"], "one_reduction": ["1", "0"], "orth_kernel": ["dma", "dma2", "reg"],
+    "host_turn": ["fast", "copy"], "small": ["host", "host-serial", "device"], "restart_sync": ["0", "1"],
+    "host_steps": ["0", "1"], "overlap": ["0", "1"], "csr_win": ["0", "1"], "spec_corr": ["1", "2", "3", "4"],
+    "exchange": ["allgather", "halo"], "reorder": ["auto", "rcm", "none"], "spmv_staged": ["auto", "0", "1"],
+    "spmv_tiles": ["auto", "0", "1"], "host_threads": ["1", "3", "64", "1000"],
+    "shift": ["lds=0", "lds=1", "batch=8", "batch=16", "batch=32", "lanes=8", "lanes=16", "lanes=32", "lanes=64", "block_inverse=0",
+              "block_inverse=256", "factor=host", "factor=device", "wave=0", "wave=1", "profile=0", "profile=1", "lanes=16,batch=16",
+              "lds=0,batch=8,lanes=32,block_inverse=0,factor=host,wave=0,profile=1"],
+}
+
+
+def test_every_option_value_is_accepted_and_read_back():
+    for name, values in OPTION_VALUES.items():
+        try:
+            for v in values:
+                sa.set_option(name, v)
+                assert sa.get_option(name) == v
+        finally:
+            sa.set_option(name, None)
+        assert sa.get_option(name) == os.environ.get("MISPEC_" + name.upper())
+
+
+@pytest.mark.parametrize("name,value", [
+    ("orth_kernel", "dam"), ("orth_kernel", "dmac"), ("orth_kernel", "dmap"), ("orth_kernel", "dmacp"), ("orth", "eager"),
+    ("small", "Device"), ("small", ""), ("host_turn", "slow"), ("exchange", "ring"), ("reorder", "amd"), ("spmv_tiles", "2"),
+    ("one_reduction", "2"), ("overlap", "off"), ("spec_corr", "9"), ("spec_corr", "0"), ("spec_corr", "-1"), ("spec_corr", "2x"),
+    ("host_threads", "0"), ("host_threads", "abc"), ("host_threads", " 3"), ("host_threads", "99999999999"), ("shift", "lanes=7"),
+    ("shift", "bogus=1"), ("shift", "lds"), ("shift", "lds=0,lds=1"), ("shift", "block_inverse=-1"), ("shift", "factor=1"),
+    ("shift", "lds=0,"), ("shift", "")])
+def test_an_option_value_without_a_meaning_is_refused(name, value):
+    # refused with the accepted values in the message, and the value in effect stays what it was
+    before = sa.get_option(name)
+    with pytest.raises(ValueError, match=r"mispec_set_option: '.*' is not a value of option %s .*; accepted: " % name):
+        sa.set_option(name, value)
+    assert sa.get_option(name) == before
+
+
+def test_the_accepted_values_are_listed_when_one_is_refused():
+    for name, accepted in [("orth_kernel", "dma | dma2 | reg"), ("spec_corr", "an integer from 1 to 4"),
+                           ("host_threads", "an integer from 1 on"), ("shift", "lanes=8|16|32|64")]:
+        with pytest.raises(ValueError) as e:
+            sa.set_option(name, "x")
+        assert accepted in str(e.value), str(e.value)
+
+
+@pytest.mark.parametrize("name", ["vq", "csr_win_iters", "csr_win_pf", "csr_win_nt", "kernel_probe", "dia2", "orth_kernal", ""])
+def test_a_removed_or_unknown_option_name_is_refused(name):
+    with pytest.raises(ValueError, match="unknown option"):
+        sa.set_option(name, "1")
+    assert sa.get_option(name) is None
+
+
+def test_an_invalid_environment_value_is_refused_when_it_is_read():
+    # MISPEC_<NAME> goes through the option's check when the library reads it: the entry point that reads it fails with
+    # MISPEC_EINVAL naming the variable (a Python ValueError), no exception crosses the C boundary; get_option shows the raw string
+    import subprocess
+    import sys
+
+    code = (
+        "import sys; sys.path.insert(0, %r)\n"
+        "import scipy.sparse as sp, spectra_amd as sa\n"
+        "M = sp.random(300, 300, density=0.05, format='csc', random_state=0)\n"
+        "print('get_option', sa.get_option('host_threads'))\n"
+        "print('ingest_threads', sa.lib().mispec_ingest_threads())\n"
+        "try:\n"
+        "    sa.mirror_triangle_host(M, 'L')\n"
+        "    print('accepted')\n"
+        "except ValueError as e:\n"
+        "    print('ValueError', e)\n"
+    ) % ROOT
+    for value, refused in (("abc", True), ("0", True), ("2", False), ("", False)):
+        env = dict(os.environ, MISPEC_HOST_THREADS=value)
+        r = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=120)
+        assert r.returncode == 0, r.stderr
+        lines = r.stdout.splitlines()
+        assert lines[0] == "get_option %s" % (value or None)
+        threads = int(lines[1].split()[1])
+        if refused:
+            assert threads == _capi.MISPEC_EINVAL
+            assert lines[2].startswith("ValueError MISPEC_HOST_THREADS: '%s' is not a value of option host_threads" % value), lines
+        else:
+            assert threads >= 1 and lines[2] == "accepted", lines
+            assert value == "" or threads <= int(value)
