@@ -73,12 +73,17 @@ private:
     std::vector<char> m_ritz_conv;
     CompInfo m_info = CompInfo::NotComputed;
 
+    // the widest basis the restart's V Q kernel takes (csrc/zfac.hip kMaxVqCols: one row of ncv complex columns in 64 KiB of LDS)
+    static constexpr Index kMaxNcv = 4096;
+
     static Index check_args(Index n, Index nev, Index ncv)
     {
         if (nev < 1 || nev > n - 1)
             throw std::invalid_argument("nev must satisfy 1 <= nev <= n - 1, n is the size of matrix");
         if (ncv <= nev || ncv > n)
             throw std::invalid_argument("ncv must satisfy nev < ncv <= n, n is the size of matrix");
+        if (ncv > kMaxNcv)
+            throw std::invalid_argument("ncv must not exceed 4096 for complex Hermitian matrices");
         return ncv > n ? n : ncv;
     }
 

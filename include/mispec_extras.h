@@ -145,6 +145,9 @@ int mispec_zcsr_spmv_host(const mispec_zcsr* A, const double* x_host, double* y_
 int mispec_zcsr_coeff(const mispec_zcsr* A, int64_t i, int64_t j, double* out_re_im); /* operator()(i, j) of the mirrored matrix */
 /* average ms of `reps` back-to-back products with lanes_per_row = 4, 8 or 16 lanes per row (0 = the default); benchmark helper */
 int mispec_zcsr_spmv_time(const mispec_zcsr* A, int lanes_per_row, int reps, float* ms_per_launch);
+/* mispec_zcsr_spmv_host with the kernel of lanes_per_row = 4, 8 or 16 lanes per row (anything else: MISPEC_EINVAL): the product of the
+ * instantiations mispec_zcsr_spmv_time measures, for tests */
+int mispec_zcsr_spmv_host_lanes(const mispec_zcsr* A, int lanes_per_row, const double* x_host, double* y_host);
 
 /* Factorisation whose operator is the device complex sparse matrix (every product stays in HBM). */
 int mispec_zfac_create_csr(mispec_ctx* ctx, const mispec_zcsr* A, int ncv, int hermitian, mispec_zfac** out);

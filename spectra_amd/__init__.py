@@ -1461,6 +1461,15 @@ class SparseHermMatProd:
         check(lib().mispec_zcsr_spmv_host(self.h, _zdp(x), _zdp(y)))
         return y
 
+    def perform_op_lanes(self, lanes_per_row, x_in):
+        """perform_op by the kernel with 4, 8 or 16 lanes per row (8 is what perform_op and the solver run)."""
+        x = _c128(x_in)
+        if x.shape != (self.cols(),):
+            raise ValueError("perform_op_lanes: x_in must have cols() entries")
+        y = np.empty(self.rows(), dtype=np.complex128)
+        check(lib().mispec_zcsr_spmv_host_lanes(self.h, int(lanes_per_row), _zdp(x), _zdp(y)))
+        return y
+
     def __matmul__(self, X):
         X = np.asarray(X, dtype=np.complex128)
         if X.ndim == 1:

@@ -155,6 +155,7 @@ SIGNATURES = {
     "mispec_zcsr_spmv_host": (C.c_int, [_vp, _dp, _dp]),
     "mispec_zcsr_coeff": (C.c_int, [_vp, C.c_int64, C.c_int64, _dp]),
     "mispec_zcsr_spmv_time": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "mispec_zcsr_spmv_host_lanes": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "mispec_hermeigs_create_csr": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vpp]),
     "mispec_hermeigs_create_dense": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vpp]),
     "mispec_hermeigs_destroy": (C.c_int, [_vp]),

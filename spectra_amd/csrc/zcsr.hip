@@ -138,22 +138,42 @@ extern "C" int64_t mispec_zcsr_rows(const mispec_zcsr* A) { return A ? A->n : 0;
 extern "C" int64_t mispec_zcsr_cols(const mispec_zcsr* A) { return A ? A->n : 0; }
 extern "C" int64_t mispec_zcsr_nnz(const mispec_zcsr* A) { return A ? A->nnz : 0; }
 
+namespace {
+
+// y_host = A x_host through the staging buffers, with `lpr` lanes per row
+void spmv_host(const mispec_zcsr* A, int lpr, const double* x_host, double* y_host)
+{
+    MISPEC_HIP(hipSetDevice(A->ctx->device));
+    if (A->stage_x.n < size_t(A->n))
+    {
+        A->stage_x.alloc(size_t(A->n));
+        A->stage_y.alloc(size_t(A->n));
+    }
+    hipStream_t s = A->ctx->stream;
+    const size_t bytes = size_t(A->n) * sizeof(double2);
+    MISPEC_HIP(hipMemcpyAsync(A->stage_x.p, x_host, bytes, hipMemcpyHostToDevice, s));
+    launch_spmv(lpr, A->n, A->rowptr.p, A->col.p, A->val.p, A->stage_x.p, A->stage_y.p, s);
+    MISPEC_HIP(hipMemcpyAsync(y_host, A->stage_y.p, bytes, hipMemcpyDeviceToHost, s));
+    MISPEC_HIP(hipStreamSynchronize(s));
+}
+
+}  // namespace
+
 extern "C" int mispec_zcsr_spmv_host(const mispec_zcsr* A, const double* x_host, double* y_host)
 {
     return guarded([&] {
         MISPEC_REQUIRE(A && x_host && y_host, "mispec_zcsr_spmv_host: NULL argument");
-        MISPEC_HIP(hipSetDevice(A->ctx->device));
-        if (A->stage_x.n < size_t(A->n))
-        {
-            A->stage_x.alloc(size_t(A->n));
-            A->stage_y.alloc(size_t(A->n));
-        }
-        hipStream_t s = A->ctx->stream;
-        const size_t bytes = size_t(A->n) * sizeof(double2);
-        MISPEC_HIP(hipMemcpyAsync(A->stage_x.p, x_host, bytes, hipMemcpyHostToDevice, s));
-        zcsr_apply(A, A->stage_x.p, A->stage_y.p, s);
-        MISPEC_HIP(hipMemcpyAsync(y_host, A->stage_y.p, bytes, hipMemcpyDeviceToHost, s));
-        MISPEC_HIP(hipStreamSynchronize(s));
+        spmv_host(A, kDefaultLanesPerRow, x_host, y_host);
+    });
+}
+
+extern "C" int mispec_zcsr_spmv_host_lanes(const mispec_zcsr* A, int lanes_per_row, const double* x_host, double* y_host)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(A && x_host && y_host, "mispec_zcsr_spmv_host_lanes: NULL argument");
+        MISPEC_REQUIRE(lanes_per_row == 4 || lanes_per_row == 8 || lanes_per_row == 16,
+                       "mispec_zcsr_spmv_host_lanes: lanes per row must be 4, 8 or 16");
+        spmv_host(A, lanes_per_row, x_host, y_host);
     });
 }
 

@@ -145,3 +145,42 @@ def test_complex_mband_million_rows(ctx):
     full = (L + sp.tril(L, -1).conj().T).tocsr()
     assert np.abs(full @ U - U * evals).max() <= 1e-9
     assert np.abs(U.conj().T @ U - np.eye(k)).max() <= 1e-10
+
+
+# Wide bases: every restart runs k_zvq with m = ncv columns staged in LDS, and ncv > 64 takes the tile heights below 64 rows
+# (R = 32 at 80, 16 at 150, 8 at 300, 4 at 600) that the cases above never reach.  The bars are this file's own.
+@pytest.mark.parametrize("rule", [sa.SortRule.LargestMagn, sa.SortRule.BothEnds], ids=lambda r: r.name)
+@pytest.mark.parametrize("n,k,m", [(2000, 30, 80), (2000, 60, 150), (3000, 100, 300), (3000, 150, 600)])
+def test_sparse_hermitian_wide_bases(ctx, n, k, m, rule):
+    A = sparse_data(n, 0.01, seed=n + m)
+    solve_and_check(sa.SparseHermMatProd(A, "L", ctx), hermitian_from_lower(A), k, m, rule)
+
+
+def test_ncv_above_4096_is_refused_at_construction(ctx):
+    """The restart's V Q kernel holds one row of ncv complex columns in 64 KiB of LDS: ncv <= 4096.  The constructor says so, not
+    the first restart after ncv Lanczos steps."""
+    n = 5000
+    op = sa.SparseHermMatProd(sp.identity(n, dtype=np.complex128, format="csc"), "L", ctx)
+    with pytest.raises(ValueError, match="4096"):
+        sa.HermEigsSolver(op, 10, 4097)
+    with pytest.raises(ValueError, match="4096"):
+        sa.HermEigsSolver(sa.DenseHermMatProd(np.eye(4100, dtype=np.complex128), "L", ctx), 10, 4100)
+    with pytest.raises(ValueError, match="ncv must satisfy"):
+        sa.HermEigsSolver(op, 10, n + 1)
+    assert sa.HermEigsSolver(op, 10, 4096).ncv == 4096  # the limit itself is taken
+
+
+def test_complex_mband_ten_million_rows(ctx):
+    """DESIGN.md section 7.1's measured solve (n = 10^7, nev = 20, ncv = 40, LargestMagn), checked."""
+    n, k, m = 10_000_000, 20, 40
+    L = workloads.herm_band(n)
+    op = sa.SparseHermMatProd(L, "L", ctx)
+    assert op.nnz() == 2 * L.nnz - n
+    eigs = sa.HermEigsSolver(op, k, m)
+    eigs.init()
+    assert eigs.compute(sa.SortRule.LargestMagn) == k and eigs.info() == sa.CompInfo.Successful
+    evals, U = eigs.eigenvalues(), eigs.eigenvectors()
+    full = (L + sp.tril(L, -1).conj().T).tocsr()
+    del L
+    assert np.abs(full @ U - U * evals).max() <= 1e-9
+    assert np.abs(U.conj().T @ U - np.eye(k)).max() <= 1e-10

@@ -73,6 +73,31 @@ def test_hermitian_restart_flow_on_a_host_backend(hostlib, n, m, k):
         hostlib.mispec_zdense_destroy(D)
 
 
+@pytest.mark.parametrize("n,m", [(331, 64), (331, 65), (523, 129), (523, 257)])
+def test_product_and_residual_checks_on_a_host_backend(hostlib, n, m):
+    """herm_checks.tile_height_checks (what tests/test_gpu_zcsr.py applies to k_zvq at every tile height) on the host backend, whose
+    V Q is a plain loop: the references, bounds and sensitivity conditions of that check at four of its widths.  The host backend
+    has no tiles; its rounding counts are its own (a product and an addition per term, one running sum over the rows)."""
+    import zprim_checks as P
+
+    A = Z.matrix(n, True, seed=n + m)
+    D, fac = C.c_void_p(), C.c_void_p()
+    Z.ok(hostlib.mispec_zdense_upload(None, n, n, Z.dp(A), n, 0, b"L", C.byref(D)))
+    Z.ok(hostlib.mispec_zfac_create_dense(None, D, m, 1, C.byref(fac)))
+    try:
+        HC.tile_height_checks(hostlib, fac, n, m, HC.host_vq_roundings, P.host_dot_roundings)
+    finally:
+        hostlib.mispec_zfac_destroy(fac)
+        hostlib.mispec_zdense_destroy(D)
+
+
+def test_every_tile_height_is_covered():
+    """The widths of the GPU run hit each tile height of k_zvq twice: at its last m (exactly 64 KiB of LDS) and its first."""
+    assert [HC.vq_rows(m) for m in HC.VQ_WIDTHS] == [64, 32, 32, 16, 16, 8, 8, 4, 4, 2, 2, 1, 1]
+    assert all(HC.vq_rows(m) * m * 16 == 65536 for m in HC.VQ_WIDTHS[0::2])
+    assert all(HC.vq_rows(m) * m * 16 <= 65536 for m in range(1, 4097))
+
+
 def test_compress_rejects_a_partial_factorisation(hostlib):
     n, m = 20, 8
     A = Z.matrix(n, True, seed=1)
