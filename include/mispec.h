@@ -65,6 +65,8 @@ const char* mispec_version(void);
  *   csr_win         1 (default) | 0                                      x windows of the int32 CSR kernel
  *   reorder         auto (default) | rcm | none                          reverse Cuthill-McKee at ingest / in the shift solve
  *   spmv_staged, spmv_tiles   auto (default) | 0 | 1                     staged / tile format for scattered patterns: never / always
+ *   spmm            auto (default) | 0 | 2 | 4 | 8                       block product (mispec_spmm): the widest panel of columns that
+ *                                                                        shares one pass over A (0: one SpMV per column; same bits)
  *   host_threads    integer >= 1                                         upper bound on the host threads of the ingest / the shift solve's
  *                                                                        host-side factorisation (tests: results do not depend on it)
  *   shift           comma list of lds=0|1, batch=8|16|32, lanes=8|16|32|64, block_inverse=<MiB>, factor=host|device, wave=0|1,
@@ -205,6 +207,19 @@ int mispec_spmv(const mispec_csr* A, const double* x_dev, double* y_dev);
 int mispec_spmv_host(const mispec_csr* A, const double* x_host, double* y_host);
 /* Y = A X for a column-major n x k block: operator* (SparseSymMatProd.h:93-96). Host pointers. */
 int mispec_spmm_host(const mispec_csr* A, const double* X_host, int64_t ldx, int k, double* Y_host, int64_t ldy);
+/* Y[:, c] = A X[:, c], c < k, with DEVICE pointers, enqueued on the context's stream: the block product behind operator* and
+ * the Davidson solver's A V.  X (cols() x k) and Y (rows() x k) are column-major with leading dimensions ldx >= cols(),
+ * ldy >= rows() and must not overlap; entries of Y between rows() and ldy are not touched.  The columns are cut into panels of
+ * 8, then 4, then 2 columns (option spmm: 2 | 4 | 8 cap the width, 0 allows none, auto — the default — uses 8 and 4, the widths
+ * that measured faster than single products), each of which reads A once from its int32 CSR arrays whatever
+ * format the SpMV of the matrix uses; remaining single columns are mispec_spmv calls.  Every (row, column) is one sum in storage
+ * order with rounded products: bit-identical to k calls of mispec_spmv.  A reordered matrix keeps the caller's index order.
+ * Unsharded matrices only.  k = 0 and a matrix without rows succeed without a launch. */
+int mispec_spmm(const mispec_csr* A, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);
+/* The cut of k columns into panels, host only (no device needed): widths_out[0 .. *count) in the order the block product
+ * runs them, each 8, 4, 2 or 1 (a single column), non-increasing, summing to k.  forced_panel: 0 = what option spmm says,
+ * 1 = single columns only, 2 | 4 | 8 = the widest panel.  MISPEC_EINVAL for k < 0, another forced_panel, or cap < *count. */
+int mispec_spmm_plan(int k, int forced_panel, int* widths_out, int cap, int* count);
 /* Symmetric reordering of an unsharded square matrix (no reference counterpart: on a CPU the ordering of the rows costs
  * little; on the GPU scattered x gathers cost an order of magnitude).  The stored matrix becomes P A P' with P from reverse
  * Cuthill-McKee on the pattern of A + A' (host, once).  Everything the C ABI hands out keeps the CALLER's index order:
@@ -256,6 +271,9 @@ int mispec_rcm_order(int64_t n, const int32_t* rowptr, const int32_t* colind, in
                      int* gave_up, int64_t* widest_level);
 /* Duration (ms, HIP events on the context stream) of the last `reps` back-to-back SpMV launches. */
 int mispec_spmv_time(const mispec_csr* A, const double* x_dev, double* y_dev, int reps, float* ms_per_launch);
+/* The same for `reps` back-to-back block products mispec_spmm(A, X_dev, ldx, k, Y_dev, ldy), packs and single columns included. */
+int mispec_spmm_time(const mispec_csr* A, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy, int reps,
+                     float* ms_per_launch);
 
 /* ---------------------------------------------------------------------------
  * Shift-and-invert operator  y = (A - sigma I)^{-1} x  for symmetric A — replaces SparseSymShiftSolve

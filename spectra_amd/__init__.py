@@ -20,7 +20,7 @@ from ._capi import MispecError, Profile, build_library, check, lib
 __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatProd", "SparseSymShiftSolve", "SymEigsSolver",
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
-           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver"]
+           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -235,6 +235,16 @@ def get_option(name):
     return None if v is None else v.decode()
 
 
+def spmm_plan(k, panel=0):
+    """The panel widths a block product of k columns runs, in order (mispec_spmm_plan; host only): each 8, 4, 2 or 1.
+    panel: 0 what option `spmm` says, 1 single columns only, 2 | 4 | 8 the widest panel."""
+    cap = max(int(k), 1)
+    out = (C.c_int * cap)()
+    count = C.c_int(0)
+    check(lib().mispec_spmm_plan(int(k), int(panel), out, cap, C.byref(count)))
+    return [out[i] for i in range(count.value)]
+
+
 def default_context():
     global _default_ctx
     if _default_ctx is None:
@@ -293,6 +303,16 @@ class _DeviceMatrix:
     def spmv_time(self, x_ptr, y_ptr, reps):
         ms = C.c_float()
         check(lib().mispec_spmv_time(self.h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), reps, C.byref(ms)))
+        return ms.value
+
+    def spmm_device(self, x_ptr, ldx, k, y_ptr, ldy):
+        """Y[:, :k] = A X[:, :k] with raw DEVICE pointers to column-major blocks (ldx >= cols(), ldy >= rows(); X and Y must not
+        overlap), enqueued on the context's stream: mispec_spmm, bit-identical to k spmv_device calls."""
+        check(lib().mispec_spmm(self.h, C.c_void_p(x_ptr), int(ldx), int(k), C.c_void_p(y_ptr), int(ldy)))
+
+    def spmm_time(self, x_ptr, ldx, k, y_ptr, ldy, reps):
+        ms = C.c_float()
+        check(lib().mispec_spmm_time(self.h, C.c_void_p(x_ptr), int(ldx), int(k), C.c_void_p(y_ptr), int(ldy), int(reps), C.byref(ms)))
         return ms.value
 
     def algorithmic_bytes(self):

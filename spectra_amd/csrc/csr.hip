@@ -1514,17 +1514,27 @@ extern "C" int mispec_spmm_host(const mispec_csr* A, const double* X_host, int64
         MISPEC_REQUIRE(ldx >= A->n_cols && ldy >= A->n_rows, "mispec_spmm_host: leading dimension too small");
         A->ctx->make_current();
         hipStream_t s = A->ctx->stream;
-        if (A->stage_x.n < size_t(A->n_cols))
-            A->stage_x.alloc(size_t(A->n_cols));
-        if (A->stage_y.n < size_t(A->n_rows))
-            A->stage_y.alloc(size_t(A->n_rows));
-        for (int c = 0; c < k; c++)
+        if (k == 0 || A->n_rows == 0)
+            return;
+        // slabs of at most 32 columns: one upload, one block product (launch_spmm, spmm.hip), one download and one
+        // synchronisation per slab.  Even leading dimensions keep every staged column 16-byte aligned.
+        constexpr int kSlab = 32;
+        const int slab = std::min(k, kSlab);
+        const int64_t lsx = round_up(std::max<int64_t>(A->n_cols, 1), 2), lsy = round_up(A->n_rows, 2);
+        if (A->stage_x.n < size_t(lsx) * slab)
+            A->stage_x.alloc(size_t(lsx) * slab);
+        if (A->stage_y.n < size_t(lsy) * slab)
+            A->stage_y.alloc(size_t(lsy) * slab);
+        for (int c = 0; c < k; c += kSlab)
         {
-            MISPEC_HIP(hipMemcpyAsync(A->stage_x.p, X_host + int64_t(c) * ldx, size_t(A->n_cols) * sizeof(double),
-                                      hipMemcpyHostToDevice, s));
-            launch_spmv(*A, A->stage_x.p, A->stage_y.p, nullptr);
-            MISPEC_HIP(hipMemcpyAsync(Y_host + int64_t(c) * ldy, A->stage_y.p, size_t(A->n_rows) * sizeof(double),
-                                      hipMemcpyDeviceToHost, s));
+            const int w = std::min(kSlab, k - c);
+            for (int j = 0; j < w && A->n_cols > 0; j++)
+                MISPEC_HIP(hipMemcpyAsync(A->stage_x.p + int64_t(j) * lsx, X_host + int64_t(c + j) * ldx, size_t(A->n_cols) * sizeof(double),
+                                          hipMemcpyHostToDevice, s));
+            launch_spmm(*A, A->stage_x.p, lsx, w, A->stage_y.p, lsy);
+            for (int j = 0; j < w; j++)
+                MISPEC_HIP(hipMemcpyAsync(Y_host + int64_t(c + j) * ldy, A->stage_y.p + int64_t(j) * lsy, size_t(A->n_rows) * sizeof(double),
+                                          hipMemcpyDeviceToHost, s));
             MISPEC_HIP(hipStreamSynchronize(s));
         }
     });

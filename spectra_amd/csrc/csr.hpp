@@ -78,6 +78,8 @@ struct mispec_csr
     bool reordered() const { return perm.p != nullptr; }
     // staging for the host-pointer paths (allocated on first use)
     mutable mispec::DevBuf<double> stage_x, stage_y;
+    // block product (spmm.hip): the panel of X interleaved, Xp[j * KB + c] = X[j + c * ldx] (allocated on first use)
+    mutable mispec::DevBuf<double> spmm_x;
 
     int64_t local_rows() const { return row_end - row_begin; }
     // 12*nnz + 4*(rows+1) + 8*cols + 8*rows  
@@ -142,6 +144,11 @@ inline int spmv_num_blocks(int64_t local_rows)
 // when reordered): what a solver that works in the permuted order calls.
 void launch_spmv(const mispec_csr& A, const double* x_dev, double* y_dev, const SpmvEpilogue* epi, hipEvent_t ev_start = nullptr,
                  hipEvent_t ev_stop = nullptr);
+// Y[:, c] = A X[:, c] for c < k in panels of 8 / 4 / 2 columns that read A once (spmm.hip; option spmm picks the widths, a
+// remaining single column is a launch_spmv).  X, Y: column-major device arrays, ldx >= n_cols, ldy >= n_rows, not overlapping;
+// the caller's index order is kept for a reordered matrix.  Bit-identical to k launch_spmv.  Unsharded matrices only; throws
+// Error(MISPEC_EINVAL) for NULL, k < 0, a leading dimension that is too small, world > 1.
+void launch_spmm(const mispec_csr& A, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);
 // block_count >= 0: only the 256-row blocks [block_first, block_first + block_count) (their rows of y, their partial records)
 void launch_spmv_raw(const mispec_csr& A, const double* x_dev, double* y_dev, const SpmvEpilogue* epi, hipEvent_t ev_start = nullptr,
                      hipEvent_t ev_stop = nullptr, int block_first = 0, int block_count = -1);

@@ -36,13 +36,14 @@ void* big_host_alloc(size_t bytes)
 // ---- options (common.hpp) ----------------------------------------------------------------------------------------------
 namespace {
 enum class Kind { choice, integer, shift };
+constexpr int kMaxValues = 6;  // a list ends at its first null entry
 struct OptionEntry
 {
     Opt id;
     const char* name;
     const char* env;          // read when the option has not been set
     Kind kind;
-    const char* values[4];    // choice: the accepted values, in the order of the option's enum in common.hpp
+    const char* values[kMaxValues];  // choice: the accepted values, in the order of the option's enum in common.hpp
     int lo, hi;               // integer: the accepted range
     const char* meaning;
 };
@@ -71,6 +72,8 @@ constexpr OptionEntry kOptions[] = {
      "reverse Cuthill-McKee ordering at ingest and of the shift solve"},
     {Opt::spmv_staged, "spmv_staged", "MISPEC_SPMV_STAGED", Kind::choice, {"auto", "0", "1"}, 0, 0, "staged SpMV format"},
     {Opt::spmv_tiles, "spmv_tiles", "MISPEC_SPMV_TILES", Kind::choice, {"auto", "0", "1"}, 0, 0, "column-blocked tile SpMV format"},
+    {Opt::spmm, "spmm", "MISPEC_SPMM", Kind::choice, {"auto", "0", "2", "4", "8"}, 0, 0,
+     "widest panel of a block product (0: one SpMV per column)"},
     {Opt::host_threads, "host_threads", "MISPEC_HOST_THREADS", Kind::integer, {}, 1, kMaxInt,
      "upper bound on the host threads of the ingest and of the shift solve's host-side factorisation"},
     {Opt::shift, "shift", "MISPEC_SHIFT", Kind::shift, {}, 0, 0, "kernel variants of the banded shift solve"},
@@ -89,7 +92,7 @@ static_assert(entries_in_order(), "kOptions is indexed by Opt");
 struct ShiftKey
 {
     const char* key;
-    const char* values[4];
+    const char* values[kMaxValues];
     int ShiftOptions::*field;
 };
 const ShiftKey kShiftKeys[] = {
@@ -142,9 +145,9 @@ const char* effective(const OptionEntry& e, std::string& out)
     return e.env;
 }
 
-int index_of(const char* const (&values)[4], const std::string& v)
+int index_of(const char* const (&values)[kMaxValues], const std::string& v)
 {
-    for (int i = 0; i < 4 && values[i]; i++)
+    for (int i = 0; i < kMaxValues && values[i]; i++)
         if (v == values[i])
             return i;
     return -1;
@@ -163,10 +166,10 @@ bool parse_int(const std::string& v, int lo, int hi, int& out)
     out = int(x);
     return x >= lo && x <= hi;
 }
-std::string join(const char* const (&values)[4], const char* sep)
+std::string join(const char* const (&values)[kMaxValues], const char* sep)
 {
     std::string s;
-    for (int i = 0; i < 4 && values[i]; i++)
+    for (int i = 0; i < kMaxValues && values[i]; i++)
         s += std::string(i ? sep : "") + values[i];
     return s;
 }

@@ -484,8 +484,15 @@ extern "C" int mispec_davidson_compute(mispec_davidson* Sp, int selection, int64
                 gvalid = 0;
             }
             // ---- AV for the new columns (SearchSpace.h:51-57)
-            for (int j = nprod; j < size; j++)
-                S.apply(S.vcol(j), S.avcol(j));
+            if (S.A && S.A->ctx->world() == 1 && size > nprod)
+            {
+                // the CSR operator: one block product that reads A once per panel (spmm.hip), the bits of the column loop
+                launch_spmm(*S.A, S.vcol(nprod), S.ldv, size - nprod, S.avcol(nprod), S.ldv);
+                S.nops += size - nprod;
+            }
+            else
+                for (int j = nprod; j < size; j++)
+                    S.apply(S.vcol(j), S.avcol(j));
             nprod = size;
             // ---- projected matrix G = V' AV (RitzPairs.h:113): new columns by V'(A v_j), the rest by symmetry
             for (int j = gvalid; j < size; j++)
