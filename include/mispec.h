@@ -67,6 +67,9 @@ const char* mispec_version(void);
  *   spmv_staged, spmv_tiles   auto (default) | 0 | 1                     staged / tile format for scattered patterns: never / always
  *   spmm            auto (default) | 0 | 2 | 4 | 8                       block product (mispec_spmm): the widest panel of columns that
  *                                                                        shares one pass over A (0: one SpMV per column; same bits)
+ *   dia_sym         auto (default) | 0 | all                             diagonal storage: a diagonal -k whose values equal +k's bit for bit
+ *                                                                        is not stored, the SpMV reads +k's entry k rows higher (auto: for
+ *                                                                        k <= 131072, all: any k, 0: store every diagonal; same bits)
  *   host_threads    integer >= 1                                         upper bound on the host threads of the ingest / the shift solve's
  *                                                                        host-side factorisation (tests: results do not depend on it)
  *   shift           comma list of lds=0|1, batch=8|16|32, lanes=8|16|32|64, block_inverse=<MiB>, factor=host|device, wave=0|1,
@@ -192,6 +195,15 @@ int mispec_csr_set_spmv_format(mispec_csr* A, int format);
 /* Bytes one SpMV with this shard has to move, x counted once.  stored = 0: the CSR/int32 figure
  * 12 nnz + 4 (rows+1) + 8 cols + 8 rows that roofline numbers are quoted on; stored != 0: with the index format in use. */
 double mispec_csr_spmv_bytes(const mispec_csr* A, int stored);
+/* Diagonal storage of this shard (format 2; all zero when it was not built): ndia diagonals, of which nstored are kept in memory
+ * and nmirrored are read from their partner +k (option dia_sym: only diagonals whose bits equal the partner's on every local
+ * row), and lead_blocks 256-row blocks in front of the first local block, ceil(largest mirrored k / 256), which hold what a
+ * mirrored read reaches above the first local row.  Any output pointer may be NULL. */
+int mispec_csr_dia_info(const mispec_csr* A, int* ndia, int* nstored, int* nmirrored, int* lead_blocks);
+/* The rule of option dia_sym, host only (no device call): for nd diagonal offsets, out_flags[i] = 1 where diagonal i may be
+ * mirrored — offsets[i] = -k < 0, +k is among the offsets and k <= reach (reach < 0: no limit) — else 0; *lead_blocks =
+ * ceil(largest such k / 256).  The ingest then keeps, of these, the diagonals that pass the bit comparison. */
+int mispec_dia_sym_plan(const int32_t* offsets, int nd, int64_t reach, int32_t* out_flags, int* lead_blocks);
 /* A(i,j) of the stored (mirrored) matrix; 0 when absent.  Replaces operator()(i,j) (SparseSymMatProd.h:101-104).
  * Only rows of this shard can be queried. */
 int mispec_csr_coeff(const mispec_csr* A, int64_t i, int64_t j, double* out);

@@ -20,7 +20,7 @@ from ._capi import MispecError, Profile, build_library, check, lib
 __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatProd", "SparseSymShiftSolve", "SymEigsSolver",
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
-           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan"]
+           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "dia_sym_plan"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -245,6 +245,17 @@ def spmm_plan(k, panel=0):
     return [out[i] for i in range(count.value)]
 
 
+def dia_sym_plan(offsets, reach=-1):
+    """The rule of option `dia_sym` (mispec_dia_sym_plan; host only): for the diagonal offsets given, (flags, lead_blocks) —
+    flags[i] is True where diagonal i = -k may be mirrored (+k present, k <= reach; reach < 0: no limit), lead_blocks =
+    ceil(largest such k / 256).  The ingest keeps, of these, the diagonals whose bits equal their partner's."""
+    offs = np.ascontiguousarray(offsets, dtype=np.int32)
+    flags = np.zeros(offs.size, dtype=np.int32)
+    lead = C.c_int(0)
+    check(lib().mispec_dia_sym_plan(_ip(offs), int(offs.size), int(reach), _ip(flags), C.byref(lead)))
+    return [bool(f) for f in flags], lead.value
+
+
 def default_context():
     global _default_ctx
     if _default_ctx is None:
@@ -335,6 +346,13 @@ class _DeviceMatrix:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(lib().mispec_csr_windows_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return {"blocks": a.value, "covered_entries": b.value, "lds_doubles": c.value}
+
+    def dia_info(self):
+        """{ndia, nstored, nmirrored, lead_blocks} of the diagonal storage (mispec_csr_dia_info; all 0: not built): nmirrored of the
+        ndia diagonals are read from their partner +k instead of being stored (option dia_sym)."""
+        a, b, c, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().mispec_csr_dia_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return {"ndia": a.value, "nstored": b.value, "nmirrored": c.value, "lead_blocks": d.value}
 
     def windows_in_use(self):
         """True when format 0 of this matrix runs the kernel with x windows (per-matrix switch and automatic rule applied)."""

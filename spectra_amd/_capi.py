@@ -96,6 +96,8 @@ SIGNATURES = {
     "mispec_csr_spmv_format": (C.c_int, [_vp]),
     "mispec_csr_set_spmv_format": (C.c_int, [_vp, C.c_int]),
     "mispec_csr_spmv_bytes": (C.c_double, [_vp, C.c_int]),
+    "mispec_csr_dia_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mispec_dia_sym_plan": (C.c_int, [_ip, C.c_int, C.c_int64, _ip, C.POINTER(C.c_int)]),
     "mispec_csr_coeff": (C.c_int, [_vp, C.c_int64, C.c_int64, _dp]),
     "mispec_csr_download": (C.c_int, [_vp, _ip, _ip, _dp]),
     "mispec_spmv": (C.c_int, [_vp, _vp, _vp]),

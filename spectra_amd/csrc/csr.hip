@@ -30,7 +30,8 @@
 //     row-block come from LDS windows found at ingest instead of one gather per entry; the arrays stay the plain int32 CSR
 //     (see the comment above k_build_windows).  The default for format 0 when the table is adopted and rows hold >= 9 entries.
 //   * k_spmv_dia_win / k_spmv_dia_win2: diagonal storage with the x windows of a block in LDS; win2 (round 5, the default) handles
-//     two rows per thread with 16-byte loads of the values.
+//     two rows per thread with 16-byte loads of the values.  Both read a lower diagonal that equals its upper partner bit for
+//     bit from that partner's array, k rows higher, instead of storing it (option dia_sym, csr_dia.hip).
 // Bound: HBM.  Algorithmic bytes per launch: 12*nnz + 4*(rows+1) + 8*cols + 8*rows (CSR with int32
 // indices); the offset-coded variant's compulsory traffic is 9*nnz + ... .
 #include "csr_kernels.hpp"
@@ -651,6 +652,7 @@ bool reorder_matrix(mispec_csr& A, const int32_t* rowptr, const int32_t* colind,
     std::swap(A.dia_ld, B->dia_ld);
     std::swap(A.ndia, B->ndia);
     std::swap(A.dia_win, B->dia_win);
+    std::swap(A.dia_plan, B->dia_plan);
     A.tiles.swap(B->tiles);
     A.staged.swap(B->staged);
     A.wtab.swap(B->wtab);

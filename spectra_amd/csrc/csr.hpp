@@ -18,6 +18,20 @@ struct mispec_dia_windows
     int idx[32];       // per diagonal: base[c] + (offset - start[c]); thread t reads xs[idx[k] + t]
 };
 
+// Mirror plan of the diagonal format (option dia_sym, csr_dia.hip): a diagonal -k whose values equal, bit for bit, those of +k
+// k rows higher is not kept; the SpMV reads A(r, r - k) as the +k array's entry of row r - k, which the workgroup of that row
+// streamed from HBM a moment earlier on the same XCD.  Stored diagonals keep their ascending order.
+struct mispec_dia_plan
+{
+    int nstored = 0;   // diagonals kept in memory ([nstored][256] per 256-row block)
+    int lead = 0;      // blocks in front of the first local block: rows a mirrored read reaches above row_begin
+    int src[32];       // per diagonal (ascending offsets): the stored array its values are read from, + kStream when the load is
+                       // the only one of its lines in a product (nontemporal; not set: a mirrored read comes back to them)
+    int shift[32];     // 0: stored; k > 0: mirrored, row r reads the array's entry of row r - k
+    static constexpr int kStream = 256;
+    constexpr int slot(int k) const { return src[k] & (kStream - 1); }  // constexpr: callable in kernels too
+};
+
 struct mispec_csr
 {
     mispec_ctx* ctx = nullptr;
@@ -37,13 +51,18 @@ struct mispec_csr
     int ndict = 0;
     bool use_codes = true;           // mispec_csr_use_offset_codes: per-matrix switch (tests compare the two kernels)
     // Diagonal storage (third format, built from the codes when the dictionary is small and the diagonals are well
-    // filled): dia[k * dia_ld + r] = A(r, r + dia_off[k]), diagonals sorted by offset, absent entries zero.  The SpMV
-    // then needs no index at all and no gather: 8 bytes per stored slot, every load coalesced.
+    // filled), diagonals sorted by offset, absent entries zero.  The SpMV then needs no index at all and no gather: 8 bytes
+    // per stored slot, every load coalesced.  Block layout (dia_ld == 0, what build_dia makes): A(r, r + dia_off[k]) of a stored
+    // diagonal k is dia[((dia_plan.lead + r / 256) * dia_plan.nstored + dia_plan.slot(k)) * 256 + r % 256]; dia_plan says which
+    // of the ndia diagonals are kept (all of them, with lead == 0, unless option dia_sym found mirrored ones: those are read from
+    // their partner's array).  dia_ld != 0 (diagonal-major, dia[k * dia_ld + r], every diagonal stored) is still read by the
+    // kernels without a plan; nothing builds it.
     mispec::DevBuf<double> dia;
     mispec::DevBuf<int32_t> dia_off;
     int64_t dia_ld = 0;
     int ndia = 0;
     mispec_dia_windows dia_win;
+    mispec_dia_plan dia_plan;
     // x windows of the int32 CSR kernel (csr.hip k_spmv_csr_win): per 256-row block a 32-int record naming at most 8 contiguous
     // ranges of x that hold the block's columns; built on the device at ingest, used by format 0 when most entries are covered.
     mispec::DevBuf<int32_t> wtab;
@@ -93,7 +112,8 @@ struct mispec_csr
     double stored_bytes_for(int format) const
     {
         if (format == 2)
-            return 8.0 * double(ndia) * double(local_rows()) + 8.0 * double(n_cols) + 8.0 * double(local_rows());
+            return 8.0 * double(dia_plan.nstored) * double(local_rows() + 256 * int64_t(dia_plan.lead)) + 8.0 * double(n_cols) +
+                   8.0 * double(local_rows());  // the stored diagonals only, their lead blocks included
         if (format == 4)  // both phases: values, indices, the product array's round trip, tables; x counted once like everywhere
             return staged.stored_bytes(local_rows(), n_cols);
         if (format == 3)  // 12 bytes per stored entry (padding included) + the chunk table; x counted once like everywhere

@@ -3,7 +3,10 @@
 // row sum's products in its order; absent entries add 0: bit-identical to it), no index, no gather.  k_spmv_dia_win2 — the
 // headline kernel — handles two rows per thread with 16-byte loads and takes x from LDS windows; k_spmv_dia_win: one row per thread
 // (unaligned operands); k_spmv_dia: direct x loads (offsets in more than 8 clusters).  Replaces SparseSymMatProd::perform_op /
-// SparseGenMatProd::perform_op (MatOp/SparseSymMatProd.h:85-90) for such matrices.  Bound: HBM, 8 nd n + 16 n bytes per product.
+// SparseGenMatProd::perform_op (MatOp/SparseSymMatProd.h:85-90) for such matrices.  Bound: HBM, 8 nstored n + 16 n bytes per product.
+// Mirrored diagonals (option dia_sym): a diagonal -k whose values equal +k's bit for bit on every local row is not stored; the two
+// windowed kernels read A(r, r - k) as the +k array's entry of row r - k — the same bits in the same place of the same sum — which
+// the workgroup of that row streamed from HBM shortly before on the same XCD (lmap gives an XCD consecutive row blocks).
 #include "csr_kernels.hpp"
 
 #include <algorithm>
@@ -19,6 +22,19 @@ namespace {
 // ---- diagonal storage -----------------------------------------------------------------------------------------------
 constexpr int kMaxDia = 32;      // diagonals of the diagonal format
 constexpr int kDiaGroup = 8;     // loads issued together per thread: 8 values + 8 x entries
+// dia_sym = auto mirrors the diagonals -k with k <= kDiaSymReach.  Measured on M-band at n = 1e7 (profiles/r15a): with
+// the five near diagonals (k <= 1001, the partner's rows at most 4 row blocks back: L2) the product takes 0.200 ms, with the two far
+// ones as well (k = 100001: 391 blocks, 8.6 MB of this XCD's traffic back — beyond L2, inside the Infinity Cache) 0.182 ms, against
+// 0.238 ms with every diagonal stored.  Nothing further out has been measured: the reach ends at 1 MiB of x (csr.hpp kFarWindow).
+constexpr int64_t kDiaSymReach = 131072;
+// mirrored reads, and the stored loads they come back to, are plain loads: nontemporal ones measured as a loss on data that is
+// read again, and nontemporal mirrored reads made no difference where they were tried (on the 16-byte variant of dia_load2's odd
+// case, profiles/r15b_bench_dia_sym_ab.jsonl)
+constexpr bool kMirrorNontemporal = false;
+// The windowed kernels' template parameter NG is the number of groups of eight diagonals, plus kDiaMir in the instantiations that
+// read the mirror plan.  A matrix with nothing mirrored (dia_sym = 0, a non-symmetric band, diagonals that differ) runs the plain
+// instantiations: every value at vrow + k * 256, nontemporal, no plan.
+constexpr int kDiaMir = 8;
 
 // One thread per row: scatter the row's values into the diagonal-major array.  `pos_of_code` maps a dictionary code to the
 // rank of its offset.  Within a row the ranks must increase strictly (columns sorted, no duplicates), else the diagonal
@@ -45,6 +61,57 @@ __global__ __launch_bounds__(256) void k_build_dia(const int32_t* __restrict__ r
     }
 }
 
+// Candidate pairs of the mirror plan: diagonal lo (offset -k) against diagonal hi (offset +k), positions in the full array.
+struct DiaPairs
+{
+    int count = 0;
+    int lo[kMaxDia / 2], hi[kMaxDia / 2], k[kMaxDia / 2];
+};
+// bad[p] = 1 unless A(r, r - k) and A(r - k, r) hold the same 64 bits for every local row r with r - k local (absent entries are
+// the +0.0 of the zeroed array on both sides; -0.0 and NaN payloads differ from it as integers)
+__global__ __launch_bounds__(256) void k_dia_sym_check(const double* __restrict__ full, int nd, int64_t nloc, DiaPairs pairs,
+                                                       int* __restrict__ bad)
+{
+    const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (r >= nloc)
+        return;
+    const unsigned long long* bits = reinterpret_cast<const unsigned long long*>(full);
+    for (int p = 0; p < pairs.count; p++)
+    {
+        const int64_t s = r - pairs.k[p];
+        if (s < 0)
+            continue;
+        const unsigned long long a = bits[(int64_t(blockIdx.x) * nd + pairs.lo[p]) * 256 + threadIdx.x];
+        const unsigned long long b = bits[((s >> 8) * nd + pairs.hi[p]) * 256 + (s & 255)];
+        if (a != b)
+            bad[p] = 1;
+    }
+}
+// full [nd][256] blocks -> the plan's layout: the stored diagonals of every block behind plan.lead zeroed blocks, and in the lead
+// what a mirrored read of the first local rows reaches: A(s, s + k) for s < 0 (local), taken from the local rows' own lower
+// entries A(s + k, s).  On an unsharded matrix those columns do not exist and the lead stays zero.
+__global__ __launch_bounds__(256) void k_dia_compact(const double* __restrict__ full, int nd, int64_t nloc, mispec_dia_plan plan,
+                                                     double* __restrict__ out)
+{
+    const int64_t lb = blockIdx.x;
+    const int t = threadIdx.x;
+    const double* src = full + lb * nd * 256 + t;
+    double* dst = out + (lb + plan.lead) * plan.nstored * 256 + t;
+    const int64_t r = lb * 256 + t;
+    for (int k = 0; k < nd; k++)
+    {
+        const double a = src[int64_t(k) * 256];
+        const int sh = plan.shift[k];
+        if (sh == 0)
+            dst[int64_t(plan.slot(k)) * 256] = a;
+        else if (r < sh && r < nloc)
+        {
+            const int64_t e = int64_t(plan.lead) * 256 + r - sh;
+            out[((e >> 8) * plan.nstored + plan.slot(k)) * 256 + (e & 255)] = a;
+        }
+    }
+}
+
 // acc + a*b with the product rounded before the sum, as the CSR kernels do it (their products pass through LDS)
 __device__ __forceinline__ double add_rounded_product(double acc, double a, double b)
 {
@@ -61,7 +128,57 @@ struct DiaArgs
     int nd;
     int col_max;
     int64_t row_begin;
+    mispec_dia_plan plan;  // where each diagonal's values are: src[] / shift[] per diagonal (read by the NG >= kDiaMir
+                           // instantiations only), [plan.nstored][256] per block, plan.lead blocks in front of block 0
 };
+// The plan's entries of the diagonals a thread keeps, read from the kernel arguments in one go at the top of a kernel (read where
+// they are used, each value load would wait for a scalar load of its own).  Entries past nd repeat the last diagonal.
+template <int N>
+struct PlanRegs
+{
+    int src[N], shift[N];
+    __device__ __forceinline__ explicit PlanRegs(const mispec_dia_plan& pl)
+    {
+#pragma unroll
+        for (int k = 0; k < N; k++)
+        {
+            src[k] = pl.src[k];
+            shift[k] = pl.shift[k];
+        }
+    }
+};
+// entry e (a row of the lead-extended block layout) of stored array src
+__device__ __forceinline__ const double* dia_src(const DiaArgs& da, int src, int64_t e)
+{
+    return da.dia + ((e >> 8) * da.plan.nstored + (src & (mispec_dia_plan::kStream - 1))) * 256 + (e & 255);
+}
+// value of a diagonal for row e of the lead-extended layout (e >= 256 lead): a stored diagonal's own entry, a mirrored one's
+// partner entry `shift` rows higher (never below entry 0: lead = ceil(largest shift / 256))
+__device__ __forceinline__ double dia_load1(const DiaArgs& da, int src, int shift, int64_t e)
+{
+    const double* q = dia_src(da, src, e - shift);
+    return (src & mispec_dia_plan::kStream) ? __builtin_nontemporal_load(q) : *q;
+}
+// rows e, e + 1 (e even).  Even shift: one aligned 16-byte load inside one block.  Odd shift: the two entries straddle two
+// aligned pairs and, once per block, two blocks, which are nstored * 256 entries apart: two 8-byte loads (they hit L2).  The
+// alternative — the aligned pair (e - shift + 1, e - shift + 2), the neighbour lane's second entry through a lane shuffle and the
+// wave's missing entry loaded by its last lane, same register count — measured 0.271 ms per product on M-band against 0.182 ms
+// with the two 8-byte loads (profiles/r15b_bench_dia_sym_ab.jsonl) and is gone.
+__device__ __forceinline__ double2 dia_load2(const DiaArgs& da, int src, int shift, int64_t e)
+{
+    const bool nt = (src & mispec_dia_plan::kStream) != 0;
+    if (shift & 1)
+    {
+        const double* q0 = dia_src(da, src, e - shift);
+        const double* q1 = dia_src(da, src, e - shift + 1);
+        if (nt)
+            return make_double2(__builtin_nontemporal_load(q0), __builtin_nontemporal_load(q1));
+        return make_double2(*q0, *q1);
+    }
+    const v2d* q = reinterpret_cast<const v2d*>(dia_src(da, src, e - shift));
+    const v2d t2 = nt ? __builtin_nontemporal_load(q) : *q;
+    return make_double2(t2.x, t2.y);
+}
 // start of thread t's column of values in row-block lb and the stride between consecutive diagonals
 __device__ __forceinline__ const double* dia_row(const DiaArgs& da, int lb, int t, int64_t& stride)
 {
@@ -149,6 +266,9 @@ __global__ __launch_bounds__(256) void k_spmv_dia_win(DiaArgs da, mispec_dia_win
 {
     extern __shared__ double xs[];
     __shared__ double red[4];
+    constexpr bool MIR = NG >= kDiaMir;
+    constexpr int NV = (NG % kDiaMir) * kDiaGroup;
+    const PlanRegs<MIR ? NV : 1> pl(da.plan);
     const int per = (nblocks + 7) >> 3;
     const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
     if (lmap >= nblocks)
@@ -179,12 +299,22 @@ __global__ __launch_bounds__(256) void k_spmv_dia_win(DiaArgs da, mispec_dia_win
     }
     const int64_t row0 = int64_t(lb) * 256;
     const int nr = int(min(int64_t(256), nrows - row0));
-    int64_t vstride;
-    const double* vrow = dia_row(da, lb, min(tid, nr - 1), vstride);
-    double v[NG * kDiaGroup];
+    double v[NV];
+    if constexpr (MIR)
+    {
+        const int64_t erow = (int64_t(da.plan.lead) + lb) * 256 + min(tid, nr - 1);  // threads past the last row repeat it
 #pragma unroll
-    for (int k = 0; k < NG * kDiaGroup; k++)
-        v[k] = __builtin_nontemporal_load(vrow + int64_t(min(k, da.nd - 1)) * vstride);
+        for (int k = 0; k < NV; k++)
+            v[k] = dia_load1(da, pl.src[k], pl.shift[k], erow);
+    }
+    else
+    {
+        int64_t vstride;
+        const double* vrow = dia_row(da, lb, min(tid, nr - 1), vstride);
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            v[k] = __builtin_nontemporal_load(vrow + int64_t(min(k, da.nd - 1)) * vstride);
+    }
     // The epilogue's operands travel with the matrix values: issued here, they are in flight during the window staging and
     // the barrier instead of costing the block a second round trip to HBM after its row sums (the kernel is bound by the
     // number of resident blocks, i.e. by latency per block: profiles/rounds_1_2/r02r_*, r03q_*).
@@ -255,7 +385,7 @@ __global__ __launch_bounds__(256) void k_spmv_dia_win(DiaArgs da, mispec_dia_win
     __syncthreads();
     double acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < NG * kDiaGroup; k++)
+    for (int k = 0; k < NV; k++)
         if (k < da.nd)
             acc = add_rounded_product(acc, v[k], xs[w.idx[k] + tid]);
     if (EPI)
@@ -291,6 +421,9 @@ __global__ __launch_bounds__(128) void k_spmv_dia_win2(DiaArgs da, mispec_dia_wi
 {
     extern __shared__ double xs[];  // windows, then 256 per-row contributions of the epilogue
     __shared__ double red[4];
+    constexpr bool MIR = NG >= kDiaMir;
+    constexpr int NV = (NG % kDiaMir) * kDiaGroup;
+    const PlanRegs<MIR ? NV : 1> pl(da.plan);
     const int per = (nblocks + 7) >> 3;
     const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
     if (lmap >= nblocks)
@@ -321,13 +454,23 @@ __global__ __launch_bounds__(128) void k_spmv_dia_win2(DiaArgs da, mispec_dia_wi
     const int64_t row0 = int64_t(lb) * 256;
     const int nr = int(min(int64_t(256), nrows - row0));
     const int r0 = 2 * tid;  // rows r0, r0 + 1 of the block (the value array is zero-padded to whole blocks)
-    const double* vrow = da.dia + int64_t(lb) * da.nd * 256 + r0;
-    double2 v[NG * kDiaGroup];
-#pragma unroll
-    for (int k = 0; k < NG * kDiaGroup; k++)
+    double2 v[NV];
+    if constexpr (MIR)
     {
-        const v2d t2 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(vrow + int64_t(min(k, da.nd - 1)) * 256));
-        v[k] = make_double2(t2.x, t2.y);
+        const int64_t erow = (int64_t(da.plan.lead) + lb) * 256 + r0;
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+            v[k] = dia_load2(da, pl.src[k], pl.shift[k], erow);
+    }
+    else
+    {
+        const double* vrow = da.dia + int64_t(lb) * da.nd * 256 + r0;
+#pragma unroll
+        for (int k = 0; k < NV; k++)
+        {
+            const v2d t2 = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(vrow + int64_t(min(k, da.nd - 1)) * 256));
+            v[k] = make_double2(t2.x, t2.y);
+        }
     }
     double2 vprev_e = make_double2(0.0, 0.0), vrow_e = make_double2(0.0, 0.0);
     double hprev_e = 0.0;
@@ -410,7 +553,7 @@ __global__ __launch_bounds__(128) void k_spmv_dia_win2(DiaArgs da, mispec_dia_wi
     __syncthreads();
     double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
-    for (int k = 0; k < NG * kDiaGroup; k++)
+    for (int k = 0; k < NV; k++)
         if (k < da.nd)
         {
             acc0 = add_rounded_product(acc0, v[k].x, xs[w.idx[k] + r0]);
@@ -462,7 +605,82 @@ __global__ __launch_bounds__(128) void k_spmv_dia_win2(DiaArgs da, mispec_dia_wi
     }
 }
 
+// The rule of option dia_sym (host only): flags[i] = 1 where diagonal i has a negative offset -k, +k is in the dictionary and
+// k <= reach (reach < 0: no limit).  Returns ceil(largest such k / 256), the lead blocks a plan of these diagonals needs.
+int dia_sym_rule(const int32_t* offs, int nd, int64_t reach, int32_t* flags)
+{
+    int64_t kmax = 0;
+    for (int i = 0; i < nd; i++)
+    {
+        flags[i] = 0;
+        const int64_t k = -int64_t(offs[i]);
+        if (k <= 0 || (reach >= 0 && k > reach))
+            continue;
+        for (int j = 0; j < nd; j++)
+            if (int64_t(offs[j]) == k)
+                flags[i] = 1;
+        if (flags[i])
+            kmax = std::max(kmax, k);
+    }
+    return int((kmax + 255) / 256);
+}
+
+// plan from the flags of the diagonals that are mirrored (offsets ascending): slots in ascending order of the stored ones
+mispec_dia_plan make_plan(const int32_t* offs, int nd, const int32_t* mirrored)
+{
+    mispec_dia_plan pl;
+    int64_t kmax = 0;
+    for (int i = 0; i < nd; i++)
+    {
+        pl.shift[i] = mirrored[i] ? -offs[i] : 0;
+        if (!mirrored[i])
+            pl.src[i] = pl.nstored++ + mispec_dia_plan::kStream;
+        else
+            kmax = std::max<int64_t>(kmax, -int64_t(offs[i]));
+    }
+    pl.lead = int((kmax + 255) / 256);
+    for (int i = 0; i < nd; i++)
+        if (mirrored[i])
+            for (int j = 0; j < nd; j++)
+                if (offs[j] == -offs[i])
+                {
+                    pl.src[j] = pl.slot(j);  // read again by the mirrored diagonal: not nontemporal, its lines stay in L2
+                    pl.src[i] = pl.slot(j) + (kMirrorNontemporal ? mispec_dia_plan::kStream : 0);
+                }
+    for (int i = nd; i < 32; i++)  // the kernels load whole groups of eight: the rest repeat the last diagonal
+    {
+        pl.src[i] = pl.src[nd - 1];
+        pl.shift[i] = pl.shift[nd - 1];
+    }
+    return pl;
+}
+
 }  // namespace
+
+extern "C" int mispec_dia_sym_plan(const int32_t* offsets, int nd, int64_t reach, int32_t* out_flags, int* lead_blocks)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(nd >= 0 && nd <= kMaxDia && (nd == 0 || (offsets && out_flags)), "mispec_dia_sym_plan: bad argument");
+        const int lead = dia_sym_rule(offsets, nd, reach, out_flags);
+        if (lead_blocks)
+            *lead_blocks = lead;
+    });
+}
+
+extern "C" int mispec_csr_dia_info(const mispec_csr* A, int* ndia, int* nstored, int* nmirrored, int* lead_blocks)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(A, "mispec_csr_dia_info: NULL argument");
+        if (ndia)
+            *ndia = A->ndia;
+        if (nstored)
+            *nstored = A->ndia ? A->dia_plan.nstored : 0;
+        if (nmirrored)
+            *nmirrored = A->ndia ? A->ndia - A->dia_plan.nstored : 0;
+        if (lead_blocks)
+            *lead_blocks = A->ndia ? A->dia_plan.lead : 0;
+    });
+}
 
 namespace mispec {
 
@@ -534,6 +752,54 @@ void build_dia(mispec_csr& A, const std::vector<int32_t>& dict)
         }
     if (ok)
         A.dia_win = w;
+    // Mirror plan (option dia_sym).  The direct kernel k_spmv_dia (no windows) keeps every diagonal.
+    const std::vector<int32_t> none(static_cast<size_t>(nd), 0);
+    A.dia_plan = make_plan(offs.data(), nd, none.data());
+    const DiaSym sym = option_choice(Opt::dia_sym, DiaSym::automatic);
+    if (!ok || sym == DiaSym::off)
+        return;
+    std::vector<int32_t> flags(static_cast<size_t>(nd), 0);
+    dia_sym_rule(offs.data(), nd, sym == DiaSym::all ? int64_t(-1) : kDiaSymReach, flags.data());
+    DiaPairs pairs;
+    int which[kMaxDia / 2];
+    for (int i = 0; i < nd; i++)
+        if (flags[size_t(i)])
+        {
+            const int p = pairs.count++;
+            which[p] = i;
+            pairs.lo[p] = i;
+            pairs.hi[p] = int(std::find(offs.begin(), offs.end(), -offs[size_t(i)]) - offs.begin());
+            pairs.k[p] = -offs[size_t(i)];
+        }
+    if (pairs.count == 0)
+        return;
+    DevBuf<int> d_asym;
+    d_asym.alloc(size_t(pairs.count));
+    MISPEC_HIP(hipMemsetAsync(d_asym.p, 0, size_t(pairs.count) * sizeof(int), st));
+    const unsigned nblk = unsigned(ld / 256);
+    hipLaunchKernelGGL(k_dia_sym_check, dim3(nblk), dim3(256), 0, st, A.dia.p, nd, nloc, pairs, d_asym.p);
+    MISPEC_HIP(hipGetLastError());
+    int asym[kMaxDia / 2] = {};
+    MISPEC_HIP(hipMemcpyAsync(asym, d_asym.p, size_t(pairs.count) * sizeof(int), hipMemcpyDeviceToHost, st));
+    MISPEC_HIP(hipStreamSynchronize(st));
+    int nmir = 0;
+    for (int p = 0; p < pairs.count; p++)
+    {
+        if (asym[p])
+            flags[size_t(which[p])] = 0;  // differs somewhere: stays stored
+        nmir += flags[size_t(which[p])];
+    }
+    if (nmir == 0)
+        return;
+    const mispec_dia_plan plan = make_plan(offs.data(), nd, flags.data());
+    DevBuf<double> packed;
+    packed.alloc(size_t(ld + 256 * int64_t(plan.lead)) * size_t(plan.nstored));
+    MISPEC_HIP(hipMemsetAsync(packed.p, 0, packed.n * sizeof(double), st));
+    hipLaunchKernelGGL(k_dia_compact, dim3(nblk), dim3(256), 0, st, A.dia.p, nd, nloc, plan, packed.p);
+    MISPEC_HIP(hipGetLastError());
+    MISPEC_HIP(hipStreamSynchronize(st));
+    A.dia.swap(packed);
+    A.dia_plan = plan;
 }
 
 void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
@@ -546,7 +812,10 @@ void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
     const hipEvent_t ev_start = L.ev_start, ev_stop = L.ev_stop;
     const double* x_dev = L.x_dev;
     double* y_dev = L.y_dev;
-        const DiaArgs da{A.dia.p, A.dia_off.p, A.dia_ld, A.ndia, int(A.n_cols - 1), A.row_begin};
+        const DiaArgs da{A.dia.p, A.dia_off.p, A.dia_ld, A.ndia, int(A.n_cols - 1), A.row_begin, A.dia_plan};
+        // with mirrored diagonals the instantiations that read the plan (NG + kDiaMir): they know the block layout only
+        const bool mir = A.dia_plan.nstored != A.ndia;
+        MISPEC_REQUIRE(!mir || (A.dia_ld == 0 && A.dia_win.nc > 0), "diagonal storage: a mirror plan needs the block layout and x windows");
         // x staged through LDS windows when the offsets form at most 8 clusters, else direct loads (k_spmv_dia)
         // two rows per thread with 16-byte loads (k_spmv_dia_win2) when the layout and the alignment allow
         const bool dia2 = A.dia_win.nc > 0 && A.dia_ld == 0 && A.ndia <= 2 * kDiaGroup &&
@@ -581,10 +850,14 @@ void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
 #define MISPEC_DIA2_G(E, P)          \
     do                               \
     {                                \
-        if (ng == 1)                 \
-            MISPEC_DIA2_W(E, 1, P);  \
-        else                         \
-            MISPEC_DIA2_W(E, 2, P);  \
+        if (ng == 1 && !mir)                   \
+            MISPEC_DIA2_W(E, 1, P);            \
+        else if (!mir)                         \
+            MISPEC_DIA2_W(E, 2, P);            \
+        else if (ng == 1)                      \
+            MISPEC_DIA2_W(E, kDiaMir + 1, P);  \
+        else                                   \
+            MISPEC_DIA2_W(E, kDiaMir + 2, P);  \
     } while (0)
             if (post)
                 MISPEC_DIA2_G(true, true);
@@ -601,7 +874,7 @@ void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
         if (A.dia_win.nc > 0)
         {
             const size_t lds = size_t(A.dia_win.total) * sizeof(double);
-            const int ng = (A.ndia + kDiaGroup - 1) / kDiaGroup;
+            const int ng = (A.ndia + kDiaGroup - 1) / kDiaGroup + (mir ? kDiaMir : 0);
 #define MISPEC_DIA_WIN_W(E, G, W)                                                                                             \
     do                                                                                                                     \
     {                                                                                                                      \
@@ -624,14 +897,22 @@ void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
 #define MISPEC_DIA_WIN_G(E)          \
     do                               \
     {                                \
-        if (ng == 1)                 \
-            MISPEC_DIA_WIN(E, 1);    \
-        else if (ng == 2)            \
-            MISPEC_DIA_WIN(E, 2);    \
-        else if (ng == 3)            \
-            MISPEC_DIA_WIN(E, 3);    \
-        else                         \
-            MISPEC_DIA_WIN(E, 4);    \
+        if (ng == 1)                           \
+            MISPEC_DIA_WIN(E, 1);              \
+        else if (ng == 2)                      \
+            MISPEC_DIA_WIN(E, 2);              \
+        else if (ng == 3)                      \
+            MISPEC_DIA_WIN(E, 3);              \
+        else if (ng == 4)                      \
+            MISPEC_DIA_WIN(E, 4);              \
+        else if (ng == kDiaMir + 1)            \
+            MISPEC_DIA_WIN(E, kDiaMir + 1);    \
+        else if (ng == kDiaMir + 2)            \
+            MISPEC_DIA_WIN(E, kDiaMir + 2);    \
+        else if (ng == kDiaMir + 3)            \
+            MISPEC_DIA_WIN(E, kDiaMir + 3);    \
+        else                                   \
+            MISPEC_DIA_WIN(E, kDiaMir + 4);    \
     } while (0)
             if (epi && e.post_scale_state)
             {
@@ -661,8 +942,16 @@ void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
                     MISPEC_DIA_WIN_POST(2);
                 else if (ng == 3)
                     MISPEC_DIA_WIN_POST(3);
-                else
+                else if (ng == 4)
                     MISPEC_DIA_WIN_POST(4);
+                else if (ng == kDiaMir + 1)
+                    MISPEC_DIA_WIN_POST(kDiaMir + 1);
+                else if (ng == kDiaMir + 2)
+                    MISPEC_DIA_WIN_POST(kDiaMir + 2);
+                else if (ng == kDiaMir + 3)
+                    MISPEC_DIA_WIN_POST(kDiaMir + 3);
+                else
+                    MISPEC_DIA_WIN_POST(kDiaMir + 4);
 #undef MISPEC_DIA_WIN_POST
 #undef MISPEC_DIA_WIN_POST_W
             }

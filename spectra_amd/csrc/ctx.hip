@@ -74,6 +74,8 @@ constexpr OptionEntry kOptions[] = {
     {Opt::spmv_tiles, "spmv_tiles", "MISPEC_SPMV_TILES", Kind::choice, {"auto", "0", "1"}, 0, 0, "column-blocked tile SpMV format"},
     {Opt::spmm, "spmm", "MISPEC_SPMM", Kind::choice, {"auto", "0", "2", "4", "8"}, 0, 0,
      "widest panel of a block product (0: one SpMV per column)"},
+    {Opt::dia_sym, "dia_sym", "MISPEC_DIA_SYM", Kind::choice, {"auto", "0", "all"}, 0, 0,
+     "diagonal storage: lower diagonals read from their mirrored upper partner (auto: those within reach, 0: none, all)"},
     {Opt::host_threads, "host_threads", "MISPEC_HOST_THREADS", Kind::integer, {}, 1, kMaxInt,
      "upper bound on the host threads of the ingest and of the shift solve's host-side factorisation"},
     {Opt::shift, "shift", "MISPEC_SHIFT", Kind::shift, {}, 0, 0, "kernel variants of the banded shift solve"},
