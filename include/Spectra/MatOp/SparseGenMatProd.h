@@ -44,6 +44,8 @@ private:
         m_mat = std::shared_ptr<mispec_csr>(raw, [](mispec_csr* p) { (void) mispec_csr_destroy(p); });
     }
 
+    SparseGenMatProd() {}  // from_device fills the members
+
 public:
     explicit SparseGenMatProd(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx = internal::CtxPtr()) :
         m_ctx(ctx ? ctx : internal::default_context())
@@ -76,6 +78,22 @@ public:
     {
         if (!ctx || !device_matrix)
             throw std::invalid_argument("SparseGenMatProd: NULL device handle");
+    }
+
+    // From a compressed matrix whose arrays already lie in DEVICE memory (DeviceSparseView, internal/Dense.h): CSR is taken as
+    // it is, CSC is transposed on the device (mispec_csr_from_device; the arrays are copied and may be freed afterwards).
+    static SparseGenMatProd from_device(const DeviceSparseView& A, internal::CtxPtr ctx = internal::CtxPtr())
+    {
+        if (A.row_major != (Flags == RowMajor))
+            throw std::invalid_argument(
+                "SparseGenMatProd: the \"Flags\" template parameter does not match the input matrix (ColMajor/RowMajor)");
+        SparseGenMatProd op;
+        op.m_ctx = ctx ? ctx : internal::default_context();
+        mispec_csr* raw = nullptr;
+        internal::check(mispec_csr_from_device(op.m_ctx.get(), A.rows, A.cols, A.outer, A.inner, A.index_bytes, A.values,
+                                               A.row_major ? 1 : 0, &raw));
+        op.m_mat = std::shared_ptr<mispec_csr>(raw, [](mispec_csr* p) { (void) mispec_csr_destroy(p); });
+        return op;
     }
 
     Index rows() const { return static_cast<Index>(mispec_csr_rows(m_mat.get())); }

@@ -53,6 +53,8 @@ private:
         m_mat = std::shared_ptr<mispec_csr>(raw, [](mispec_csr* p) { (void) mispec_csr_destroy(p); });
     }
 
+    SparseSymMatProd() {}  // from_device fills the members
+
 public:
     // From a compressed sparse matrix in host memory.
     explicit SparseSymMatProd(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx = internal::CtxPtr()) :
@@ -89,6 +91,25 @@ public:
     {
         if (!ctx || !device_matrix)
             throw std::invalid_argument("SparseSymMatProd: NULL device handle");
+    }
+
+    // From one triangle of a compressed matrix whose arrays already lie in DEVICE memory (DeviceSparseView, internal/Dense.h):
+    // mirrored and indexed on the device, no round trip through the host (mispec_csr_from_triangle_device; the arrays are
+    // copied and may be freed afterwards).  Same argument checks and exception types as the host constructor.
+    static SparseSymMatProd from_device(const DeviceSparseView& A, internal::CtxPtr ctx = internal::CtxPtr())
+    {
+        if (A.rows != A.cols)
+            throw std::invalid_argument("SparseSymMatProd: matrix must be square");
+        if (A.row_major != (Flags == RowMajor))
+            throw std::invalid_argument(
+                "SparseSymMatProd: the \"Flags\" template parameter does not match the input matrix (ColMajor/RowMajor)");
+        SparseSymMatProd op;
+        op.m_ctx = ctx ? ctx : internal::default_context();
+        mispec_csr* raw = nullptr;
+        internal::check(mispec_csr_from_triangle_device(op.m_ctx.get(), A.rows, A.outer, A.inner, A.index_bytes, A.values,
+                                                        Uplo == Lower ? 'L' : 'U', A.row_major ? 1 : 0, &raw));
+        op.m_mat = std::shared_ptr<mispec_csr>(raw, [](mispec_csr* p) { (void) mispec_csr_destroy(p); });
+        return op;
     }
 
     Index rows() const { return static_cast<Index>(mispec_csr_rows(m_mat.get())); }

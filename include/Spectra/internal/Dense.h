@@ -213,6 +213,19 @@ struct SparseView
     bool row_major = false;
 };
 
+// A borrowed view of a compressed sparse matrix whose arrays lie in DEVICE memory (SparseSymMatProd::from_device,
+// SparseGenMatProd::from_device): outer[outer_size+1] and inner[nnz] are integers of index_bytes = 4 (int32) or 8 (int64)
+// bytes, values[nnz] doubles; the caller has finished writing them.  Only the addresses pass through these headers.
+struct DeviceSparseView
+{
+    Index rows = 0, cols = 0;
+    const void* outer = nullptr;
+    const void* inner = nullptr;
+    const double* values = nullptr;
+    int index_bytes = 4;
+    bool row_major = false;
+};
+
 // A borrowed view of a dense matrix in host memory: rows x cols with leading dimension ld, column-major
 // (Eigen's default) unless row_major.
 template <typename Scalar>

@@ -146,6 +146,48 @@ int mispec_csr_from_csc(mispec_ctx* ctx, int64_t n_rows, int64_t n_cols, const i
  * uplo: 'L' or 'U'.  row_major: 0 = CSC input (Eigen::ColMajor), 1 = CSR input (Eigen::RowMajor). */
 int mispec_csr_from_triangle(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
                              const double* val_host, char uplo, int row_major, mispec_csr** out);
+/* ---- ingest from DEVICE memory (spectra_amd/csrc/ingest_dev.hip) ----------------------------------------------------------
+ * The same three matrices from compressed arrays that already lie in HBM (a torch.sparse_csr / sparse_csc tensor, arrays
+ * assembled by the caller's kernels).  outer_dev / inner_dev are arrays of index_bytes = 4 (int32) or 8 (int64, range-checked and
+ * narrowed) bytes per index, val_dev of doubles; outer has n + 1 entries and need not start at 0.
+ * Contract:
+ *   - the inputs are read on the context's stream and COPIED; the call returns after that stream is synchronised, so the
+ *     caller may free or overwrite them at once;
+ *   - the caller must have finished writing the inputs before the call (work queued on another stream is not waited for: the
+ *     Python layer synchronises torch's current stream first);
+ *   - the matrix that comes out cannot be told apart from the one the matching host entry point (mispec_csr_upload,
+ *     mispec_csr_from_csc, mispec_csr_from_triangle) builds from the same arrays: mispec_csr_download, the SpMV format, offset
+ *     codes, diagonal storage, x windows, reordering / permutation, staged and tile formats and every product are equal bit for bit;
+ *   - validation runs on the device and is reported through a flag read by the host, never as a fault: a decreasing outer
+ *     array, an index outside [0, n) (or [0, n_cols) / [0, n_rows)), a 64-bit index beyond int32, too many entries for int32
+ *     row pointers give MISPEC_EINVAL with the host check's wording.  outer is checked before anything indexes with it;
+ *   - MISPEC_EINVAL, with a message that names the reason, also for: a sharded context or one with a communicator attached (row
+ *     shards from device arrays are not supported), index_bytes other than 4 or 8, a NULL argument (also when the matrix has no
+ *     entries: pass any valid device address then);
+ *   - mispec_last_ingest_info is filled: [0] the call, [1] the device mirror, [2] validation / transposition of a general
+ *     matrix, [3] the index formats; the host stages' slots when the host path takes over (below);
+ *   - patterns whose structures are built by host code — reverse Cuthill-McKee, the staged image, the tiles: more than a quarter
+ *     of the entries further than 131072 from the diagonal with n >= 262144, or options reorder=rcm, spmv_staged=1,
+ *     spmv_tiles=1 — download the full CSR once and continue through the host path; banded, stencil and mesh matrices never do.
+ *     A matrix with a row of more than 2^20 entries hands its (validated) input to the host routine too: the device orders a
+ *     row with (row length)^2 compares.
+ * Peak device memory of the triangle ingest, everything resident together (E_in entries in, E_out <= 2 E_in entries out, n rows,
+ * w = index_bytes): input (w + 8) E_in + w (n + 1), output 12 (E_out + 12) + 4 (n + 1), scratch 16 E_out + 4 n + 4 ceil((n + 1) /
+ * 2048) — about (w + 8) E_in + 28 E_out + (w + 8) n bytes; the scratch is freed before the index formats are built. */
+/* general matrix, CSR (row_major = 1: taken as it is, like mispec_csr_upload) or CSC (0: transposed, every row in column
+ * order and stable within equal columns, like mispec_csr_from_csc), device arrays */
+int mispec_csr_from_device(mispec_ctx* ctx, int64_t n_rows, int64_t n_cols, const void* outer_dev, const void* inner_dev,
+                           int index_bytes, const double* val_dev, int row_major, mispec_csr** out);
+/* symmetric operator from one triangle (uplo, row_major as for mispec_csr_from_triangle), device arrays */
+int mispec_csr_from_triangle_device(mispec_ctx* ctx, int64_t n, const void* outer_dev, const void* inner_dev, int index_bytes,
+                                    const double* val_dev, char uplo, int row_major, mispec_csr** out);
+/* test hook: the mirrored matrix of a triangle into caller-provided DEVICE arrays (rowptr_dev_out: n + 1 ints; colind_dev_out /
+ * val_dev_out: `capacity` entries, twice the input's always suffice); *nnz_out = entries written.  Equal to
+ * mispec_mirror_triangle_host byte for byte for every input that routine accepts (unsorted inner indices, duplicates, entries in
+ * the ignored triangle, empty rows; values compared as 64-bit integers). */
+int mispec_mirror_triangle_device(mispec_ctx* ctx, int64_t n, const void* outer_dev, const void* inner_dev, int index_bytes,
+                                  const double* val_dev, char uplo, int row_major, int32_t* rowptr_dev_out, int32_t* colind_dev_out,
+                                  double* val_dev_out, int64_t capacity, int64_t* nnz_out);
 /* Synthetic benchmark matrices generated directly in HBM (SURVEY.md §8d "M-band"): row i holds columns
  * i+off for off in {0} U {+-offsets[k]} inside [0,n); value = counter hash of (seed, min(i,j), max(i,j))
  * (symmetric) or (seed, i, j) (non-symmetric) mapped to U(-0.5,0.5).  Bit-identical to oracle/synth_matrix.h. */
@@ -252,7 +294,8 @@ int mispec_csr_tiles_info(const mispec_csr* A, int64_t* segments, int64_t* entri
  * 8192-column blocks to even counts), batches (<= 1024 entries of one bin, the unit of phase 2) and the chunks they are made of
  * (runs that are contiguous in phase-1 order). */
 int mispec_csr_staged_info(const mispec_csr* A, int64_t* bins, int64_t* slots, int64_t* batches, int64_t* chunks);
-/* Wall-clock seconds of the host stages of the last mispec_csr_upload / mispec_csr_from_triangle on the calling thread:
+/* Wall-clock seconds of the stages of the last mispec_csr_upload / mispec_csr_from_triangle (or their *_device counterparts,
+ * whose slots are listed with them) on the calling thread:
  * [0] the whole call, [1] triangle -> full matrix, [2] validation + local row pointers, [3] index formats (offset codes, diagonal
  * storage) incl. the H2D copies of the CSR arrays, [4] far-gather statistics + reordering, [5] tile image on the host, [6] its
  * upload and split, [8] staged image on the host, [9] its upload.  count <= 10 values are written. */

@@ -20,7 +20,7 @@ from ._capi import MispecError, Profile, build_library, check, lib
 __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatProd", "SparseSymShiftSolve", "SymEigsSolver",
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
-           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "dia_sym_plan"]
+           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "dia_sym_plan", "mirror_triangle_device"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -461,6 +461,72 @@ class _reorder_env:
                 os.environ["MISPEC_REORDER"] = self.old
 
 
+_TORCH_ACCEPTED = ("a 2-D torch.sparse_csr or torch.sparse_csc tensor on the context's GPU with int32 or int64 indices and float64 "
+                   "(or float32, widened) values")
+
+
+def _torch_compressed(t, ctx):
+    """(rows, cols, outer, inner, values, row_major, ctx) of a torch sparse_csr / sparse_csc tensor in device memory: the three
+    component tensors (contiguous, values as float64), which the caller keeps alive over the library call.  Anything else is
+    refused before a library call is made; torch is imported here only."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("expected %s, got %s" % (_TORCH_ACCEPTED, type(t).__name__))
+    if t.layout not in (torch.sparse_csr, torch.sparse_csc):
+        raise ValueError("expected %s, got layout %s" % (_TORCH_ACCEPTED, t.layout))
+    if not t.is_cuda:
+        raise ValueError("expected %s, got a tensor on %s (the host constructors take scipy matrices)" % (_TORCH_ACCEPTED, t.device))
+    if t.dim() != 2:
+        raise ValueError("expected %s, got a batched tensor of %d dimensions" % (_TORCH_ACCEPTED, t.dim()))
+    ctx = ctx or default_context()
+    if t.device.index != ctx.device:
+        raise ValueError("expected %s, got a tensor on %s while the context is on device %d" % (_TORCH_ACCEPTED, t.device, ctx.device))
+    row_major = t.layout == torch.sparse_csr
+    outer, inner = (t.crow_indices(), t.col_indices()) if row_major else (t.ccol_indices(), t.row_indices())
+    val = t.values()
+    if val.dtype == torch.float32:
+        val = val.to(torch.float64)
+    if val.dtype != torch.float64 or outer.dtype not in (torch.int32, torch.int64) or inner.dtype != outer.dtype:
+        raise ValueError("expected %s, got values %s and indices %s / %s" % (_TORCH_ACCEPTED, val.dtype, outer.dtype, inner.dtype))
+    outer, inner, val = outer.contiguous(), inner.contiguous(), val.contiguous()
+    if val.numel() == 0:  # empty tensors have no address; the library wants one (it reads no entry)
+        inner = torch.zeros(1, dtype=outer.dtype, device=t.device)
+        val = torch.zeros(1, dtype=torch.float64, device=t.device)
+    torch.cuda.current_stream(t.device).synchronize()  # the library reads on the context's stream
+    return t.shape[0], t.shape[1], outer, inner, val, row_major, ctx
+
+
+def _from_device(cls, ctx, reorder, call):
+    h = C.c_void_p()
+    with _reorder_env(reorder):
+        check(call(C.byref(h)))
+    obj = cls.__new__(cls)
+    _DeviceMatrix.__init__(obj, ctx, h)
+    return obj
+
+
+def mirror_triangle_device(t, uplo="L", ctx=None):
+    """The full symmetric CSR matrix of the `uplo` triangle of a torch sparse_csr / sparse_csc tensor on the GPU, mirrored by
+    the device kernels (mispec_mirror_triangle_device): (rowptr, colind, val) as numpy arrays.  Test hook: equal to
+    mirror_triangle_host byte for byte."""
+    import torch
+
+    n, nc, outer, inner, val, row_major, ctx = _torch_compressed(t, ctx)
+    if n != nc:
+        raise ValueError("mirror_triangle_device: matrix must be square")
+    cap = 2 * int(t.values().numel()) + 1
+    rp = torch.zeros(n + 1, dtype=torch.int32, device=t.device)
+    ci = torch.zeros(cap, dtype=torch.int32, device=t.device)
+    v = torch.zeros(cap, dtype=torch.float64, device=t.device)
+    torch.cuda.current_stream(t.device).synchronize()
+    nnz = C.c_int64(0)
+    check(lib().mispec_mirror_triangle_device(ctx.h, n, outer.data_ptr(), inner.data_ptr(), outer.element_size(), val.data_ptr(),
+                                             uplo.encode()[0:1], int(row_major), rp.data_ptr(), ci.data_ptr(), v.data_ptr(), cap,
+                                             C.byref(nnz)))
+    return rp.cpu().numpy(), ci[:nnz.value].cpu().numpy(), v[:nnz.value].cpu().numpy()
+
+
 class SparseSymMatProd(_DeviceMatrix):
     """MatOp/SparseSymMatProd.h: y = selfadjointView<Uplo>(A) * x; only the `uplo` triangle of A is read."""
 
@@ -480,6 +546,27 @@ class SparseSymMatProd(_DeviceMatrix):
         """The synthetic symmetric benchmark matrix of SURVEY.md §8(d), generated directly in HBM."""
         return _synth(cls, n, offsets, seed, True, ctx)
 
+    @classmethod
+    def from_torch(cls, t, uplo="L", ctx=None, reorder=None):
+        """The operator of the `uplo` triangle of a torch.sparse_csr / sparse_csc tensor that lives on the context's GPU
+        (int32 or int64 indices, float64 or widened float32 values), built on the device: nothing is copied to the host unless
+        the pattern needs a host-built structure (reordering, staged image, tiles).  The tensor is copied; it may be freed or
+        overwritten afterwards.  Equal to SparseSymMatProd(scipy matrix of the same arrays) bit for bit."""
+        n, nc, outer, inner, val, row_major, ctx = _torch_compressed(t, ctx)
+        if n != nc:
+            raise ValueError("SparseSymMatProd: matrix must be square")
+        return cls.from_device_pointers(n, outer.data_ptr(), inner.data_ptr(), outer.element_size(), val.data_ptr(), row_major,
+                                        uplo=uplo, ctx=ctx, reorder=reorder)
+
+    @classmethod
+    def from_device_pointers(cls, n, outer_ptr, inner_ptr, index_bytes, val_ptr, row_major, uplo="L", ctx=None, reorder=None):
+        """from_torch for callers without torch: raw DEVICE addresses of outer (n + 1 indices), inner and the float64 values of
+        one triangle, index_bytes = 4 or 8 (mispec_csr_from_triangle_device; the caller has finished writing them)."""
+        ctx = ctx or default_context()
+        return _from_device(cls, ctx, reorder, lambda out: lib().mispec_csr_from_triangle_device(
+            ctx.h, int(n), C.c_void_p(outer_ptr), C.c_void_p(inner_ptr), int(index_bytes), C.c_void_p(val_ptr), uplo.encode()[0:1],
+            int(bool(row_major)), out))
+
 
 class SparseGenMatProd(_DeviceMatrix):
     """MatOp/SparseGenMatProd.h: y = A * x for a general sparse A (CSR or CSC input)."""
@@ -496,6 +583,22 @@ class SparseGenMatProd(_DeviceMatrix):
     @classmethod
     def synth_band(cls, n, offsets=BAND_OFFSETS, seed=SYNTH_SEED, ctx=None):
         return _synth(cls, n, offsets, seed, False, ctx)
+
+    @classmethod
+    def from_torch(cls, t, ctx=None, reorder=None):
+        """The operator of a general torch.sparse_csr (taken as it is) or sparse_csc (transposed on the device) tensor on the
+        context's GPU; see SparseSymMatProd.from_torch.  Equal to SparseGenMatProd(scipy matrix of the same arrays)."""
+        nr, nc, outer, inner, val, row_major, ctx = _torch_compressed(t, ctx)
+        return cls.from_device_pointers(nr, nc, outer.data_ptr(), inner.data_ptr(), outer.element_size(), val.data_ptr(), row_major,
+                                        ctx=ctx, reorder=reorder)
+
+    @classmethod
+    def from_device_pointers(cls, n_rows, n_cols, outer_ptr, inner_ptr, index_bytes, val_ptr, row_major, ctx=None, reorder=None):
+        """Raw DEVICE addresses of a compressed general matrix (mispec_csr_from_device): CSR when row_major, else CSC."""
+        ctx = ctx or default_context()
+        return _from_device(cls, ctx, reorder, lambda out: lib().mispec_csr_from_device(
+            ctx.h, int(n_rows), int(n_cols), C.c_void_p(outer_ptr), C.c_void_p(inner_ptr), int(index_bytes), C.c_void_p(val_ptr),
+            int(bool(row_major)), out))
 
 
 def _synth(cls, n, offsets, seed, symmetric, ctx):

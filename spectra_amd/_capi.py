@@ -80,6 +80,9 @@ SIGNATURES = {
     "mispec_csr_upload": (C.c_int, [_vp, C.c_int64, C.c_int64, _ip, _ip, _dp, _vpp]),
     "mispec_csr_from_csc": (C.c_int, [_vp, C.c_int64, C.c_int64, _ip, _ip, _dp, _vpp]),
     "mispec_csr_from_triangle": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_char, C.c_int, _vpp]),
+    "mispec_csr_from_device": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_int, _vpp]),
+    "mispec_csr_from_triangle_device": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_char, C.c_int, _vpp]),
+    "mispec_mirror_triangle_device": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int, _vp, C.c_char, C.c_int, _vp, _vp, _vp, C.c_int64, _lp]),
     "mispec_csr_synth_band": (C.c_int, [_vp, C.c_int64, C.c_uint64, _lp, C.c_int, C.c_int, _vpp]),
     "mispec_csr_destroy": (C.c_int, [_vp]),
     "mispec_csr_rows": (C.c_int64, [_vp]),

@@ -36,6 +36,7 @@
 // indices); the offset-coded variant's compulsory traffic is 9*nnz + ... .
 #include "csr_kernels.hpp"
 #include "reorder.hpp"
+#include "ingest.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -760,6 +761,16 @@ void interior_blocks(const mispec_csr& A, int64_t col_lo, int64_t col_hi, int& f
     }
     first = best_first;
     count = best;
+}
+
+// ingest.hpp: the host ingest's pieces that the device ingest (ingest_dev.hip) shares
+void csr_alloc_entries(mispec_csr& A, int64_t nnz) { alloc_entries(A, nnz); }
+void csr_alloc_codes(mispec_csr& A) { alloc_codes(A); }
+double* ingest_seconds() { return g_ingest; }
+mispec_csr* csr_upload_host(mispec_ctx* ctx, int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* colind,
+                            const double* val, bool structurally_symmetric)
+{
+    return upload_rows(ctx, n_rows, n_cols, rowptr, colind, val, true, structurally_symmetric);
 }
 
 int spmv_rows_per_block() { return 256; }
