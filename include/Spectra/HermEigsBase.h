@@ -333,6 +333,13 @@ public:
         const int flags = one_reduction ? MISPEC_ORTH_ONE_REDUCTION : MISPEC_ORTH_TWO_REDUCTIONS;
         internal::check(mispec_fac_set_orth_mode(m_fac.handle(), on ? (MISPEC_ORTH_ONESWEEP | flags) : MISPEC_ORTH_REFERENCE));
     }
+    // ... and, with `wide`, on bases of 129 to 512 columns as well (opt-in; include/mispec.h MISPEC_ORTH_WIDE: from step 128 on the
+    // pass over V goes in column panels).  Without it such bases keep the reference's control flow.  Call before init().
+    void set_onesweep_orthogonalization(bool on, bool one_reduction, bool wide)
+    {
+        const int flags = (one_reduction ? MISPEC_ORTH_ONE_REDUCTION : MISPEC_ORTH_TWO_REDUCTIONS) | (wide ? MISPEC_ORTH_WIDE : 0);
+        internal::check(mispec_fac_set_orth_mode(m_fac.handle(), on ? (MISPEC_ORTH_ONESWEEP | flags) : MISPEC_ORTH_REFERENCE));
+    }
 
 private:
     // The Ritz vectors of H belonging to the converged wanted values, as columns (reference :455-465)

@@ -51,6 +51,7 @@ const char* mispec_version(void);
  * message lists the accepted values.  A value from the environment is checked when the library reads it: the call that reads it
  * fails with MISPEC_EINVAL naming the variable.  Names and values:
  *   orth            onesweep (default) | onesweep-eager | reference      control flow of the Lanczos steps at creation
+ *                   | onesweep-wide                                      (onesweep-wide: one-sweep steps up to ncv = 512, MISPEC_ORTH_WIDE)
  *   one_reduction   1 (default) | 0                                      one reduction per one-sweep step
  *   orth_kernel     dma | dma2 | reg                                     the orthogonalisation passes: LDS-DMA ring of three / two slots,
  *                                                                        or registers (unset: dma from 131072 rows on, else reg)
@@ -466,7 +467,15 @@ int mispec_fac_f_norm(const mispec_fac* fac, double* beta);  /* f_norm() */
  *     the lagged path and continues with the reference's loop.  Effective for ncv <= 128 on standard problems over every operator that
  *     works on device pointers (device matrices incl. the product operator A'A / AA' of the SVD solver, the shift solve of
  *     SymEigsShiftSolver, dense matrices, user operators on device pointers, the Cholesky mode of the generalized problem);
- *     ignored otherwise (B-inner-product modes of the generalized problem, user operators with host pointers, wider bases).  For 64 < ncv <= 128 every sweep ends the reference's way (no fused restart).
+ *     ignored otherwise (B-inner-product modes of the generalized problem, user operators with host pointers, and bases wider
+ *     than 128 columns unless MISPEC_ORTH_WIDE is set).  For ncv > 64 every sweep ends the reference's way (no fused restart).
+ *   MISPEC_ORTH_ONESWEEP | MISPEC_ORTH_WIDE (opt-in; option orth=onesweep-wide): the one-sweep steps on bases of up to 512 columns
+ *     as well.  Steps with fewer than 128 finished columns run the same kernels as without the flag; from step 128 on the pass
+ *     goes in panels of 64 columns (all panels but the last subtract their part of the pending correction into column i, the
+ *     last one finishes the step, then the others' dot products follow: DESIGN.md 3.2.4) — every panel but the last is read
+ *     twice, where the reference flow reads the basis about three times.  Same records, same decisions, same exits from the
+ *     lagged path.  513 <= ncv <= 1024 and row-sharded contexts with ncv > 128 keep the reference flow, and mispec_fac_orth_info
+ *     then reports MISPEC_ORTH_REFERENCE.  mispec_fac_panel_steps counts the lagged steps that ran in panelled form.
  * mispec_fac_orth_info reports the mode in effect, the lagged steps executed, how often the lagged path was left because a
  * column needed a second correction (check_stops) or a correction could not be carried (state_stops), the largest accepted
  * |c|/|f| and the largest |V'v| measured after a lagged correction. */
@@ -478,6 +487,7 @@ enum { MISPEC_ORTH_REFERENCE = 0, MISPEC_ORTH_ONESWEEP = 1,
                                               its own before the pass.  Neither flag: the library default — one reduction, MISPEC_ONE_REDUCTION=0 in the environment
                                               restores two */
        MISPEC_ORTH_TWO_REDUCTIONS = 0x1000,
+       MISPEC_ORTH_WIDE = 0x2000,          /* one-sweep steps on bases of 129 to 512 columns too, in column panels (above) */
        MISPEC_ORTH_TEST_RESTART_CHECK = 0x400 /* test hook: the device-side test of every fused restart reports "one correction was not
                                                 enough", so none of the steps enqueued behind the restart runs and the host continues
                                                 with the reference's loop before the sweep is enqueued again (see below) */ };
@@ -492,6 +502,7 @@ int mispec_fac_set_orth_mode(mispec_fac* fac, int mode);
  * norms are still measured).  The first step of a sweep and every step after the reference's own loop take the two-reduction
  * form.  mispec_fac_onered_steps counts the steps that took the one-reduction form. */
 int mispec_fac_onered_steps(const mispec_fac* fac, int64_t* steps);
+int mispec_fac_panel_steps(const mispec_fac* fac, int64_t* steps); /* lagged steps in column panels (MISPEC_ORTH_WIDE) */
 int mispec_fac_orth_info(const mispec_fac* fac, int* mode, int64_t* lagged_steps, int64_t* check_stops, int64_t* state_stops,
                          double* max_rel_c, double* max_chk);
 /* One-sweep mode, end of a full sweep (factorize up to ncv): the correction of the LAST step stays pending as well, and
@@ -642,13 +653,15 @@ int mispec_symeigs_exchange_info(const mispec_symeigs* s, int* halo, int64_t* re
 int mispec_symeigs_overlap_info(const mispec_symeigs* s, int* first_block, int* block_count, int* total_blocks);
 int mispec_symeigs_profile(mispec_symeigs* s, int enable);
 /* Orthogonalisation scheme of the Lanczos steps (see mispec_fac_set_orth_mode): MISPEC_ORTH_ONESWEEP (default) or
- * MISPEC_ORTH_REFERENCE, the reference's two-pass control flow.  Call before init() / compute(). */
+ * MISPEC_ORTH_REFERENCE, the reference's two-pass control flow; MISPEC_ORTH_ONESWEEP | MISPEC_ORTH_WIDE extends the one-sweep
+ * steps to 128 < ncv <= 512.  Call before init() / compute(). */
 int mispec_symeigs_set_orth_mode(mispec_symeigs* s, int mode);
 int mispec_symeigs_orth_info(const mispec_symeigs* s, int* mode, int64_t* lagged_steps, int64_t* check_stops,
                              int64_t* state_stops, double* max_rel_c, double* max_chk);
 int mispec_symeigs_restart_info(const mispec_symeigs* s, int64_t* fused, int64_t* recorrected); /* see mispec_fac_restart_info */
 int mispec_symeigs_turn_info(const mispec_symeigs* s, int64_t* turns, double* host_seconds, int64_t* fallbacks); /* see mispec_fac_turn_info */
 int mispec_symeigs_onered_steps(const mispec_symeigs* s, int64_t* steps);                        /* see mispec_fac_onered_steps */
+int mispec_symeigs_panel_steps(const mispec_symeigs* s, int64_t* steps);                         /* see mispec_fac_panel_steps */
 
 /* ---------------------------------------------------------------------------
  * General (non-symmetric) solver: Spectra::GenEigsSolver<Spectra::SparseGenMatProd<double>> behind a handle.

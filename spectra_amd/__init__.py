@@ -32,8 +32,10 @@ SYNTH_SEED = 20240607
 # "onesweep-restart-check" is the test hook of the restart without a host turn: its device-side test always reports a failure
 # "onesweep-onered" / "onesweep-twored": one reduction per lagged step (include/mispec.h MISPEC_ORTH_ONE_REDUCTION) or the separate
 # alpha reduction, whatever the library default is
+# "onesweep-wide" (opt-in, MISPEC_ORTH_WIDE): the one-sweep steps on bases of 129 to 512 columns too, in column panels from step 128 on
 ORTH_MODES = {"reference": 0, "onesweep": 1, "onesweep-eager": 1 | 0x100, "onesweep-recorrect": 1 | 0x200, "onesweep-restart-check": 1 | 0x400,
-              "onesweep-onered": 1 | 0x800, "onesweep-twored": 1 | 0x1000, "onesweep-onered-eager": 1 | 0x800 | 0x100}
+              "onesweep-onered": 1 | 0x800, "onesweep-twored": 1 | 0x1000, "onesweep-onered-eager": 1 | 0x800 | 0x100,
+              "onesweep-wide": 1 | 0x2000, "onesweep-wide-onered": 1 | 0x2000 | 0x800, "onesweep-wide-twored": 1 | 0x2000 | 0x1000}
 
 
 def _orth_mode_value(mode):
@@ -1125,8 +1127,10 @@ class SymEigsSolver:
     def set_orth_mode(self, mode):
         """'onesweep' (default: the correction of a step rides on the next step's pass over V, include/mispec.h
         mispec_fac_set_orth_mode) or 'reference' (Lanczos.h:145-181, two passes over V per step; also MISPEC_ORTH=reference in
-        the environment).  Call before init().  Where the one-sweep steps do not apply (ncv > 128, generalized problems, host-pointer user
-        operators) the reference flow runs whatever is set: orth_info()['mode'] says which one is in effect."""
+        the environment).  'onesweep-wide' (opt-in) extends the one-sweep steps to 128 < ncv <= 512: from step 128 on the pass
+        goes in column panels (orth_info()['panel_steps'] counts those steps).  Call before init().  Where the one-sweep steps
+        do not apply (ncv > 128 without 'onesweep-wide', ncv > 512, ncv > 128 on a row-sharded context, generalized problems,
+        host-pointer user operators) the reference flow runs whatever is set: orth_info()['mode'] says which one is in effect."""
         check(lib().mispec_symeigs_set_orth_mode(self.h, _orth_mode_value(mode)))
 
     def orth_info(self):
@@ -1137,7 +1141,10 @@ class SymEigsSolver:
         check(lib().mispec_symeigs_restart_info(self.h, C.byref(fused), C.byref(again)))
         ored = C.c_int64(0)
         check(lib().mispec_symeigs_onered_steps(self.h, C.byref(ored)))
+        pan = C.c_int64(0)
+        check(lib().mispec_symeigs_panel_steps(self.h, C.byref(pan)))
         return {"mode": "onesweep" if (mode.value & 0xFF) else "reference", "eager_last": bool(mode.value & 0x100),
+                "wide": bool(mode.value & 0x2000), "panel_steps": pan.value,
                 "recorrect_hook": bool(mode.value & 0x200), "one_reduction": bool(mode.value & 0x800), "lagged_steps": a.value, "check_stops": b.value,
                 "state_stops": c.value, "max_rel_c": r.value, "max_chk": k.value, "fused_restarts": fused.value,
                 "fused_recorrected": again.value, "one_reduction_steps": ored.value}
@@ -1840,8 +1847,19 @@ class Factorization:
         check(lib().mispec_fac_init(self.h, _dp(v0), C.byref(self.nmatop)))
 
     def set_orth_mode(self, mode):
-        """'onesweep' (default) or 'reference' (mispec_fac_set_orth_mode); call before factorize_from."""
+        """'onesweep' (default), 'onesweep-wide' (one-sweep steps up to m = 512) or 'reference' (mispec_fac_set_orth_mode);
+        call before factorize_from."""
         check(lib().mispec_fac_set_orth_mode(self.h, _orth_mode_value(mode)))
+
+    def orth_info(self):
+        """The mode in effect and the counters of the one-sweep steps (mispec_fac_orth_info, mispec_fac_panel_steps)."""
+        mode, a, b, c = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        r, k, pan = C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+        check(lib().mispec_fac_orth_info(self.h, C.byref(mode), C.byref(a), C.byref(b), C.byref(c), C.byref(r), C.byref(k)))
+        check(lib().mispec_fac_panel_steps(self.h, C.byref(pan)))
+        return {"mode": "onesweep" if (mode.value & 0xFF) else "reference", "wide": bool(mode.value & 0x2000),
+                "one_reduction": bool(mode.value & 0x800), "lagged_steps": a.value, "check_stops": b.value, "state_stops": c.value,
+                "max_rel_c": r.value, "max_chk": k.value, "panel_steps": pan.value}
 
     def init_random(self, seed=0):
         check(lib().mispec_fac_init_random(self.h, seed, C.byref(self.nmatop)))

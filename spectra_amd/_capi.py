@@ -274,6 +274,8 @@ SIGNATURES = {
     "mispec_get_option": (C.c_char_p, [C.c_char_p]),
     "mispec_fac_onered_steps": (C.c_int, [_vp, _lp]),
     "mispec_symeigs_onered_steps": (C.c_int, [_vp, _lp]),
+    "mispec_fac_panel_steps": (C.c_int, [_vp, _lp]),
+    "mispec_symeigs_panel_steps": (C.c_int, [_vp, _lp]),
     "mispec_symeigs_restart_info": (C.c_int, [_vp, _lp, _lp]),
     "mispec_geneigs_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vpp]),
     "mispec_geneigs_create_op": (C.c_int, [_vp, op_fn, _vp, C.c_int64, C.c_int64, C.c_int64, _vpp]),

@@ -148,7 +148,7 @@ enum class Opt
     spmv_staged, spmv_tiles, spmm, dia_sym, host_threads, shift, count
 };
 // the values of the choice options, in the order of their entries' lists (`unset` is no value: the option not given)
-enum class Orth { onesweep, onesweep_eager, reference };
+enum class Orth { onesweep, onesweep_eager, reference, onesweep_wide };
 enum class OrthKernel { dma, dma2, reg, unset };
 enum class HostTurn { fast, copy };
 enum class Small { host, host_serial, device };

@@ -49,7 +49,7 @@ struct OptionEntry
 };
 constexpr int kMaxInt = 0x7fffffff;
 constexpr OptionEntry kOptions[] = {
-    {Opt::orth, "orth", "MISPEC_ORTH", Kind::choice, {"onesweep", "onesweep-eager", "reference"}, 0, 0,
+    {Opt::orth, "orth", "MISPEC_ORTH", Kind::choice, {"onesweep", "onesweep-eager", "reference", "onesweep-wide"}, 0, 0,
      "control flow of the Lanczos steps of the factorisations created afterwards"},
     {Opt::one_reduction, "one_reduction", "MISPEC_ONE_REDUCTION", Kind::choice, {"0", "1"}, 0, 0,
      "one reduction per one-sweep step (default 1)"},

@@ -117,6 +117,10 @@ struct mispec_fac
     // On by default since round 4 (set at creation from MISPEC_ORTH, default "onesweep"); mispec_fac_set_orth_mode /
     // MISPEC_ORTH=reference select the reference's two-pass control flow.
     bool onesweep = true;
+    // MISPEC_ORTH_WIDE (opt-in): bases of 129 to 512 columns take the one-sweep steps too, from step 128 on in column panels
+    // (orth_wide.hip); panel_steps counts those steps.  Not on a row-sharded context (onesweep_max_cols).
+    bool orth_wide = false;
+    int64_t panel_steps = 0;
     double lag_limit = 1e-6;
     int64_t lag_steps = 0, lag_check_stops = 0, lag_state_stops = 0;
     double lag_rel_c_max = 0.0, lag_chk_max = 0.0;
@@ -1202,7 +1206,16 @@ void lanczos_step_lagged(mispec_fac& F, int i, bool last, bool defer)
         a.status = &st->status;
         a.onered = onered ? 1 : 0;
         Timed t(F, FAM_VTF);
-        F.count_bytes(FAM_VTF, i + 4);  // i columns, f and w read; column i and f written
+        if (i < 2 * kPanelCols)
+            F.count_bytes(FAM_VTF, i + 4);  // i columns, f and w read; column i and f written
+        else
+        {
+            // in panels (orth_wide.hip), counted with a pending correction: every panel but the last is read twice (subtract:
+            // + running vector read and written; dots: + f and column i read), the last one once (+ running vector and w read,
+            // column i and f written)
+            const int rest = (i - 1) / kPanelCols * kPanelCols;
+            F.count_bytes(FAM_VTF, 2 * rest + 4 * (rest / kPanelCols) + (i - rest) + 4);
+        }
         const int nrec = launch_orth(*F.ctx, ORTH_LAGGED, a);
         fin.mode = kFinishLagged;
         fin.alpha_src = F.alpha_slot();
@@ -1254,6 +1267,11 @@ bool default_one_reduction()
 
 bool device_operator(const mispec_fac& F) { return F.A != nullptr || (F.S != nullptr && F.Bcsr == nullptr) || F.D != nullptr || F.dop != nullptr; }
 
+// Widest basis whose steps take the one-sweep form: 128 columns (k_orth_lagged with 4 or 8 wavefronts); with MISPEC_ORTH_WIDE
+// 512 — a record holds 2 i + 1 <= kMaxCols slots, and from step 128 on the pass runs in column panels (orth_wide.hip).  A
+// row-sharded context keeps 128: its records travel packed, with sum f^2 and <f~, A f~> behind the 2 i + 1 slots.
+int onesweep_max_cols(const mispec_fac& F) { return (F.orth_wide && !F.sharded()) ? kMaxCols / 2 : 2 * kPanelCols; }
+
 // Lanczos.h:62-187
 void factorize_lanczos(mispec_fac& F, int from_k, int to_m, int64_t* nmatop)
 {
@@ -1263,8 +1281,9 @@ void factorize_lanczos(mispec_fac& F, int from_k, int to_m, int64_t* nmatop)
     // (their Lanczos epilogue is a kernel of its own that reads H(i,i-1) and the stop flag from device memory), and the Cholesky
     // mode of the generalized problem: L^{-1} A L^{-T} is a standard symmetric operator made of three enqueued products
     const bool fast = F.device_steps && device_operator(F) && !F.bmode();
-    // standard problems (incl. the product operator of the SVD solver); bases of up to 128 columns (k_orth_lagged with 4 or 8 wavefronts)
-    const bool lagged = fast && F.onesweep && F.m <= 2 * kPanelCols;
+    // standard problems (incl. the product operator of the SVD solver); bases of up to 128 columns (k_orth_lagged with 4 or 8
+    // wavefronts), of up to 512 with MISPEC_ORTH_WIDE
+    const bool lagged = fast && F.onesweep && F.m <= onesweep_max_cols(F);
     // a sweep that completes the factorisation is followed by a restart (or by nothing that needs f): its last correction can wait
     // — for the fused restart (k_vq_fused: one column panel); wider bases finish every sweep the reference's way
     const bool defer = lagged && F.m <= kPanelCols && to_m == F.m && !F.eager_last && !F.eager_sticky && !small_on_device();
@@ -1325,6 +1344,8 @@ void factorize_lanczos(mispec_fac& F, int from_k, int to_m, int64_t* nmatop)
             F.onered_steps += hs.onered_steps;
             F.lag_rel_c_max = std::max(F.lag_rel_c_max, hs.lag_rel_c_max);
             F.lag_chk_max = std::max(F.lag_chk_max, hs.lag_chk_max);
+            // the steps i .. last_done of this run whose pass went in column panels (128 or more finished columns)
+            F.panel_steps += std::max(0, last_done - std::max(i, 2 * kPanelCols) + 1);
         }
         for (int j = i; j <= last_done; j++)  // bring H of the executed steps home
         {
@@ -1834,6 +1855,7 @@ int fac_create_impl(mispec_ctx* ctx, const mispec_csr* A, const mispec_symshift*
                 const Orth mode = option_choice(Opt::orth, Orth::onesweep);
                 F->onesweep = mode != Orth::reference;
                 F->eager_last = mode == Orth::onesweep_eager;
+                F->orth_wide = mode == Orth::onesweep_wide;
                 F->onered = F->onesweep && default_one_reduction();
             }
             F->h_red.alloc(kPartialLd + 8);
@@ -2027,12 +2049,13 @@ extern "C" int mispec_fac_set_orth_mode(mispec_fac* fac, int mode)
         MISPEC_REQUIRE((base == MISPEC_ORTH_REFERENCE && flags == 0) ||
                            (base == MISPEC_ORTH_ONESWEEP &&
                             (flags & ~(MISPEC_ORTH_EAGER_LAST | MISPEC_ORTH_TEST_RECORRECT | MISPEC_ORTH_TEST_RESTART_CHECK |
-                                       MISPEC_ORTH_ONE_REDUCTION | MISPEC_ORTH_TWO_REDUCTIONS)) == 0),
+                                       MISPEC_ORTH_ONE_REDUCTION | MISPEC_ORTH_TWO_REDUCTIONS | MISPEC_ORTH_WIDE)) == 0),
                        "mispec_fac_set_orth_mode: unknown mode");
         fac->onesweep = (base == MISPEC_ORTH_ONESWEEP);
         fac->eager_last = (flags & MISPEC_ORTH_EAGER_LAST) != 0;
         fac->test_recorrect = (flags & MISPEC_ORTH_TEST_RECORRECT) != 0;
         fac->test_restart_check = (flags & MISPEC_ORTH_TEST_RESTART_CHECK) != 0;
+        fac->orth_wide = (flags & MISPEC_ORTH_WIDE) != 0;
         if (flags & MISPEC_ORTH_ONE_REDUCTION)
             fac->onered = true;
         else if (flags & MISPEC_ORTH_TWO_REDUCTIONS)
@@ -2047,12 +2070,14 @@ extern "C" int mispec_fac_orth_info(const mispec_fac* fac, int* mode, int64_t* l
 {
     return guarded([&] {
         MISPEC_REQUIRE(fac, "mispec_fac_orth_info: NULL argument");
-        const bool active = fac->onesweep && fac->device_steps && fac->symmetric && device_operator(*fac) && !fac->bmode() && fac->m <= 2 * kPanelCols;
+        const bool active = fac->onesweep && fac->device_steps && fac->symmetric && device_operator(*fac) && !fac->bmode() &&
+                            fac->m <= onesweep_max_cols(*fac);
         if (mode)
             *mode = active ? (MISPEC_ORTH_ONESWEEP | ((fac->eager_last || fac->eager_sticky) ? MISPEC_ORTH_EAGER_LAST : 0) |
                               (fac->test_recorrect ? MISPEC_ORTH_TEST_RECORRECT : 0) |
                               (fac->test_restart_check ? MISPEC_ORTH_TEST_RESTART_CHECK : 0) |
-                              (fac->onered ? MISPEC_ORTH_ONE_REDUCTION : 0))
+                              (fac->onered ? MISPEC_ORTH_ONE_REDUCTION : 0) |
+                              ((fac->orth_wide && !fac->sharded()) ? MISPEC_ORTH_WIDE : 0))
                            : MISPEC_ORTH_REFERENCE;
         if (lagged_steps)
             *lagged_steps = fac->lag_steps;
@@ -2072,6 +2097,14 @@ extern "C" int mispec_fac_onered_steps(const mispec_fac* fac, int64_t* steps)
     return guarded([&] {
         MISPEC_REQUIRE(fac && steps, "mispec_fac_onered_steps: NULL argument");
         *steps = fac->onered_steps;
+    });
+}
+
+extern "C" int mispec_fac_panel_steps(const mispec_fac* fac, int64_t* steps)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(fac && steps, "mispec_fac_panel_steps: NULL argument");
+        *steps = fac->panel_steps;
     });
 }
 

@@ -436,6 +436,10 @@ extern "C" int mispec_symeigs_onered_steps(const mispec_symeigs* s, int64_t* ste
 {
     return s ? mispec_fac_onered_steps(s->fac(), steps) : MISPEC_EINVAL;
 }
+extern "C" int mispec_symeigs_panel_steps(const mispec_symeigs* s, int64_t* steps)
+{
+    return s ? mispec_fac_panel_steps(s->fac(), steps) : MISPEC_EINVAL;
+}
 extern "C" int mispec_symeigs_turn_info(const mispec_symeigs* s, int64_t* turns, double* host_seconds, int64_t* fallbacks)
 {
     return s ? mispec_fac_turn_info(s->fac(), turns, host_seconds, fallbacks) : MISPEC_EINVAL;

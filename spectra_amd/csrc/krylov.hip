@@ -1667,11 +1667,14 @@ int launch_orth_panel(const mispec_ctx& ctx, OrthMode mode, const OrthArgs& a, i
 //   CORRECT_*    dst = src - V c needs every panel before V'dst: the panels subtract one after the other, the last
 //                one (where dst is final) also computes |dst|^2 and its part of V'dst, then the other panels' parts
 //                follow on the finished dst.  V is read 1.5 times instead of once — the price of ncv > 64.
+//   LAGGED       up to 127 finished columns: one launch (k_orth_lagged).  From 128 on (bases of 129 to 512 columns, opt-in): v_i
+//                needs every panel's part of V c_in, so all panels but the last subtract into column i, the last one finishes
+//                the step as the one-panel kernel does, and the others' dot products with f and v_i follow (orth_wide.hip)
 int launch_orth(const mispec_ctx& ctx, OrthMode mode, const OrthArgs& a)
 {
     MISPEC_REQUIRE(a.ncol >= 0 && a.ncol <= kMaxCols, "orth kernel: more than 1024 basis columns");
-    MISPEC_REQUIRE(mode != ORTH_LAGGED || (a.ncol >= 1 && a.ncol < 2 * kPanelCols), "one-sweep orth kernel: needs 1 <= columns <= 127");
-    if (a.ncol <= kPanelCols || mode == ORTH_LAGGED)
+    MISPEC_REQUIRE(mode != ORTH_LAGGED || (a.ncol >= 1 && 2 * a.ncol + 1 <= kMaxCols), "one-sweep orth kernel: needs 1 <= columns <= 511");
+    if (a.ncol <= kPanelCols || (mode == ORTH_LAGGED && a.ncol < 2 * kPanelCols))
     {
         OrthArgs one = a;
         one.col0 = 0;
@@ -1729,7 +1732,18 @@ int launch_orth(const mispec_ctx& ctx, OrthMode mode, const OrthArgs& a)
                     launch_orth_panel(ctx, ORTH_VTF, b, grid);
                 }
             break;
-        case ORTH_LAGGED:  // single panel only (checked above)
+        case ORTH_LAGGED:  // 128 or more finished columns (opt-in, MISPEC_ORTH_WIDE): subtract, finish, dots (orth_wide.hip)
+            for (int q = 0; q + 1 < npan; q++)
+            {
+                // column i <- f - V_0 c_0 - ... - V_q c_q, un-normalised; f stays intact until the last panel has read it.
+                // No pending correction: c_in counts as zero, the launches exit at once and the last panel starts from f.
+                OrthArgs b = panel(q);
+                b.src = (q == 0) ? a.vi : a.vout;
+                b.dst = a.vout;
+                b.need_corr = a.pending;
+                launch_orth_panel(ctx, ORTH_CORRECT_ONLY, b, grid);
+            }
+            launch_orth_lagged_wide(ctx, a, grid);
             break;
     }
     return grid;

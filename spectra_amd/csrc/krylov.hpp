@@ -22,7 +22,8 @@ enum OrthMode
     ORTH_CORRECT_ONLY = 3, // dst = src - V c_in ; |dst|^2              (Arnoldi.h:254-255)
     // One-sweep variant (opt-in, fac.hip lanczos_step_lagged; NOT the reference's control flow):
     //   v_i = (f - V c_in)/beta -> vout ;  chk = V' v_i ;  dst = w - alpha v_i ;  c = [V, v_i]' dst ; |dst|^2
-    // i.e. the correction of step i-1 and the projection of step i in ONE pass over V[:, :ncol], ncol = i <= 63.
+    // i.e. the correction of step i-1 and the projection of step i in ONE pass over V[:, :ncol], ncol = i <= 127; in column
+    // panels for 128 <= i <= 511 (orth_wide.hip).
     // Record slots: [0, i) c ; i <v_i, dst> ; [i+1, 2i+1) chk ; kSlotBeta2 / kSlotMaxAbs of dst.
     ORTH_LAGGED = 4
 };
@@ -139,6 +140,10 @@ int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_o
 // The other modes (reference flow, Arnoldi) the same way (orth_dma_modes.hip): one column panel, vectors of at least 1024 tiles.
 bool orth_dma_modes_eligible(OrthMode mode, const OrthArgs& a);
 int launch_orth_dma_mode(const mispec_ctx& ctx, OrthMode mode, const OrthArgs& a);
+
+// ORTH_LAGGED with 128 <= a.ncol <= 511 finished columns (orth_wide.hip; called by launch_orth behind the subtracting launches):
+// the last panel's finishing pass and the other panels' dot products, all on `grid` workgroups.
+void launch_orth_lagged_wide(const mispec_ctx& ctx, const OrthArgs& a, int grid);
 
 // All launchers enqueue on ctx.stream and return immediately.
 int launch_orth(const mispec_ctx& ctx, OrthMode mode, const OrthArgs& a);  // returns the number of partial records
