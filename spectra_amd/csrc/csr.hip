@@ -22,7 +22,7 @@
 //   (the two variants below live in files of their own since round 6: csr_dia.hip and csr_win.hip; launch_spmv_raw here picks the
 //   format and hands an SpmvLaunch to launch_spmv_dia / launch_spmv_csr_win; shared device helpers: csr_kernels.hpp)
 //   * diagonal variant (k_spmv_dia): when the dictionary has at most 32 diagonals and they are at least 3/4 full,
-//     the values are also kept diagonal-major (dia[k][row], zero where the matrix has no entry) and
+//     the values are also kept by diagonal (dia[k][row] within a 256-row block, zero where the matrix has no entry) and
 //     y[r] = sum_k dia[k][r] * x[r + off_k] in ascending offset order — no index, no gather, no LDS, every load
 //     coalesced, 8 bytes per stored slot.  Same products in the same order as the CSR row sum (absent entries add 0), so
 //     again bit-identical.
@@ -68,11 +68,8 @@ __global__ __launch_bounds__(kThreads) void k_spmv_csr_stream(const int32_t* __r
     __shared__ double red[4];
     __shared__ int dict_s[CODES ? kMaxDict : 1];
 
-    // XCD-aware map: gridDim.x == 8 * per; block b runs on XCD b % 8 and takes the (b/8)-th
-    // row-block of that XCD's contiguous range.
-    const int per = (nblocks + 7) >> 3;
-    const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
-    if (lmap >= nblocks)
+    const int lmap = spmv_block_of_launch(nblocks);
+    if (lmap < 0)
         return;
     const int lb = epi.first_block + lmap;  // a launch may cover a sub-range of the row-blocks (comm / compute overlap)
     if (EPI && epi.status && *epi.status != 0)
@@ -650,7 +647,6 @@ bool reorder_matrix(mispec_csr& A, const int32_t* rowptr, const int32_t* colind,
     A.dia.swap(B->dia);
     A.dia_off.swap(B->dia_off);
     std::swap(A.ndict, B->ndict);
-    std::swap(A.dia_ld, B->dia_ld);
     std::swap(A.ndia, B->ndia);
     std::swap(A.dia_win, B->dia_win);
     std::swap(A.dia_plan, B->dia_plan);
@@ -838,9 +834,7 @@ void launch_spmv_raw(const mispec_csr& A, const double* x_dev, double* y_dev, co
     const int nblocks = block_count;  // the kernels map blockIdx onto [first_block, first_block + nblocks)
     MISPEC_REQUIRE(!(epi && epi->post_scale_state) || spmv_can_post_scale(A),
                    "SpMV: a post-scaled step start was requested for a matrix that cannot take it");
-    const int per = (nblocks + 7) >> 3;
-    const int threads = spmv_rows_per_block();
-    const dim3 grid(unsigned(per * 8)), block(static_cast<unsigned>(threads));
+    const dim3 grid(spmv_grid_blocks(nblocks)), block(static_cast<unsigned>(spmv_rows_per_block()));
     SpmvEpilogue e = epi ? *epi : SpmvEpilogue{};
     e.first_block = block_first;
     const int format = A.spmv_format();
@@ -864,18 +858,6 @@ void launch_spmv_raw(const mispec_csr& A, const double* x_dev, double* y_dev, co
         launch_spmv_dia(A, L);  // csr_dia.hip
         return;
     }
-    // With an event pair the launch is timed through the dispatch's own completion signal (start/stop of the
-    // kernel itself, as a profiler sees it) instead of marker packets around it.
-#define MISPEC_SPMV_LAUNCH(K)                                                                                          \
-    do                                                                                                                 \
-    {                                                                                                                  \
-        if (ev_start && ev_stop)                                                                                       \
-            hipExtLaunchKernelGGL((K), grid, block, 0, A.ctx->stream, ev_start, ev_stop, 0, A.rowptr.p, A.colind.p,   \
-                                  A.val.p, x_dev, y_dev, nloc, nblocks, e, cd);                                       \
-        else                                                                                                           \
-            hipLaunchKernelGGL((K), grid, block, 0, A.ctx->stream, A.rowptr.p, A.colind.p, A.val.p, x_dev, y_dev,    \
-                               nloc, nblocks, e, cd);                                                                  \
-    } while (0)
     // up to 16 entries per row on average: the 16 KiB-chunk instantiation.  Measured in the solver loop: 7 per row (reordered
     // stencil) 0.258 -> 0.215 ms, 15 per row (M-band) 0.413 -> 0.394 ms, stand-alone equal
     // (round 4, profiles/r07a: on M-band the two chunk sizes measure alike in the loop, 0.417-0.422 ms, in both step flows)
@@ -885,22 +867,18 @@ void launch_spmv_raw(const mispec_csr& A, const double* x_dev, double* y_dev, co
         launch_spmv_csr_win(A, L);  // csr_win.hip
         return;
     }
-#define MISPEC_SPMV(E)                                                    \
-    do                                                                    \
-    {                                                                     \
-        if (small_chunk)                                                  \
-            MISPEC_SPMV_LAUNCH((k_spmv_csr_stream<E, false, 256, false, 2>)); \
-        else if (coded)                                                   \
-            MISPEC_SPMV_LAUNCH((k_spmv_csr_stream<E, false, 256, true>)); \
-        else                                                              \
-            MISPEC_SPMV_LAUNCH((k_spmv_csr_stream<E, false, 256, false>)); \
-    } while (0)
-    if (epi)
-        MISPEC_SPMV(true);
-    else
-        MISPEC_SPMV(false);
-#undef MISPEC_SPMV
-#undef MISPEC_SPMV_LAUNCH
+    const auto launch = [&](auto kernel) {
+        launch_kernel(kernel, grid, block, 0, A.ctx->stream, ev_start, ev_stop, A.rowptr.p, A.colind.p, A.val.p, x_dev, y_dev, nloc,
+                      nblocks, e, cd);
+    };
+    with_bool(epi != nullptr, [&](auto E) {
+        if (small_chunk)
+            launch(k_spmv_csr_stream<E(), false, 256, false, 2>);
+        else if (coded)
+            launch(k_spmv_csr_stream<E(), false, 256, true>);
+        else
+            launch(k_spmv_csr_stream<E(), false, 256, false>);
+    });
     MISPEC_HIP(hipGetLastError());
 }
 

@@ -52,14 +52,12 @@ struct mispec_csr
     bool use_codes = true;           // mispec_csr_use_offset_codes: per-matrix switch (tests compare the two kernels)
     // Diagonal storage (third format, built from the codes when the dictionary is small and the diagonals are well
     // filled), diagonals sorted by offset, absent entries zero.  The SpMV then needs no index at all and no gather: 8 bytes
-    // per stored slot, every load coalesced.  Block layout (dia_ld == 0, what build_dia makes): A(r, r + dia_off[k]) of a stored
+    // per stored slot, every load coalesced.  Block layout: A(r, r + dia_off[k]) of a stored
     // diagonal k is dia[((dia_plan.lead + r / 256) * dia_plan.nstored + dia_plan.slot(k)) * 256 + r % 256]; dia_plan says which
     // of the ndia diagonals are kept (all of them, with lead == 0, unless option dia_sym found mirrored ones: those are read from
-    // their partner's array).  dia_ld != 0 (diagonal-major, dia[k * dia_ld + r], every diagonal stored) is still read by the
-    // kernels without a plan; nothing builds it.
+    // their partner's array).
     mispec::DevBuf<double> dia;
     mispec::DevBuf<int32_t> dia_off;
-    int64_t dia_ld = 0;
     int ndia = 0;
     mispec_dia_windows dia_win;
     mispec_dia_plan dia_plan;

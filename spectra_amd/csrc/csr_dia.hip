@@ -27,21 +27,18 @@ constexpr int kDiaGroup = 8;     // loads issued together per thread: 8 values +
 // ones as well (k = 100001: 391 blocks, 8.6 MB of this XCD's traffic back — beyond L2, inside the Infinity Cache) 0.182 ms, against
 // 0.238 ms with every diagonal stored.  Nothing further out has been measured: the reach ends at 1 MiB of x (csr.hpp kFarWindow).
 constexpr int64_t kDiaSymReach = 131072;
-// mirrored reads, and the stored loads they come back to, are plain loads: nontemporal ones measured as a loss on data that is
-// read again, and nontemporal mirrored reads made no difference where they were tried (on the 16-byte variant of dia_load2's odd
-// case, profiles/r15b_bench_dia_sym_ab.jsonl)
-constexpr bool kMirrorNontemporal = false;
 // The windowed kernels' template parameter NG is the number of groups of eight diagonals, plus kDiaMir in the instantiations that
 // read the mirror plan.  A matrix with nothing mirrored (dia_sym = 0, a non-symmetric band, diagonals that differ) runs the plain
 // instantiations: every value at vrow + k * 256, nontemporal, no plan.
+// (the encoding stays: bench.py and tests/test_host_profiles.py parse the demangled <EPI, NG, NCW, POST> by position)
 constexpr int kDiaMir = 8;
 
-// One thread per row: scatter the row's values into the diagonal-major array.  `pos_of_code` maps a dictionary code to the
-// rank of its offset.  Within a row the ranks must increase strictly (columns sorted, no duplicates), else the diagonal
+// One thread per row: scatter the row's values into the [nd][256] piece of its 256-row block.  `pos_of_code` maps a dictionary
+// code to the rank of its offset.  Within a row the ranks must increase strictly (columns sorted, no duplicates), else the diagonal
 // sum would not be the CSR row sum bit for bit: such matrices raise *bad and keep the CSR kernels.
 __global__ __launch_bounds__(256) void k_build_dia(const int32_t* __restrict__ rowptr, const uint8_t* __restrict__ codes,
                                                    const double* __restrict__ val, const int32_t* __restrict__ pos_of_code,
-                                                   int64_t nloc, int64_t ld, double* __restrict__ dia, int* __restrict__ bad, int nd_blocked)
+                                                   int64_t nloc, int nd, double* __restrict__ dia, int* __restrict__ bad)
 {
     const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
     if (r >= nloc)
@@ -53,11 +50,7 @@ __global__ __launch_bounds__(256) void k_build_dia(const int32_t* __restrict__ r
         if (pos <= last)
             *bad = 1;
         last = pos;
-        // nd_blocked > 0: the values of a 256-row block are one contiguous [nd][256] piece (one stream per workgroup)
-        if (nd_blocked)
-            dia[(int64_t(blockIdx.x) * nd_blocked + pos) * 256 + threadIdx.x] = val[p];
-        else
-            dia[int64_t(pos) * ld + r] = val[p];
+        dia[(int64_t(blockIdx.x) * nd + pos) * 256 + threadIdx.x] = val[p];
     }
 }
 
@@ -122,9 +115,8 @@ __device__ __forceinline__ double add_rounded_product(double acc, double a, doub
 
 struct DiaArgs
 {
-    const double* dia;
+    const double* dia;  // block layout: dia[(block * nd + k) * 256 + r % 256] without a plan
     const int32_t* off;
-    int64_t ld;       // diagonal-major layout: dia[k * ld + r]; 0: block layout dia[(block * nd + k) * 256 + r % 256]
     int nd;
     int col_max;
     int64_t row_begin;
@@ -179,16 +171,27 @@ __device__ __forceinline__ double2 dia_load2(const DiaArgs& da, int src, int shi
     const v2d t2 = nt ? __builtin_nontemporal_load(q) : *q;
     return make_double2(t2.x, t2.y);
 }
-// start of thread t's column of values in row-block lb and the stride between consecutive diagonals
-__device__ __forceinline__ const double* dia_row(const DiaArgs& da, int lb, int t, int64_t& stride)
+
+// The post-scaled step start (POST instantiations of the windowed kernels): reads beta = |f| from the step state, takes the
+// beta < sqrt(eps) stop and records H(i,i-1) = beta.  Every block takes the same decision from the same beta; one thread (`first`)
+// records it (Lanczos.h:99-128 without the restart branch).  Returns whether the block goes on.
+__device__ __forceinline__ bool post_scaled_step_start(const SpmvEpilogue& epi, bool first, double& beta)
 {
-    if (da.ld == 0)
+    StepState* st = static_cast<StepState*>(epi.post_scale_state);
+    beta = st->beta;
+    if (beta < epi.post_scale_eps_sqrt)
     {
-        stride = 256;
-        return da.dia + int64_t(lb) * da.nd * 256 + t;
+        if (first)
+        {
+            st->status = kStepSmallBeta;
+            st->stop_step = epi.post_scale_step;
+            st->stop_count = 0;
+        }
+        return false;
     }
-    stride = da.ld;
-    return da.dia + int64_t(lb) * 256 + t;
+    if (first)
+        st->subd[epi.post_scale_step - 1] = beta;
+    return true;
 }
 
 template <bool EPI>
@@ -197,11 +200,8 @@ __global__ __launch_bounds__(256) void k_spmv_dia(DiaArgs da, const double* __re
 {
     __shared__ int off_s[kMaxDia];
     __shared__ double red[4];
-    // same XCD-aware row-block map and the same 256-row blocks as k_spmv_csr_stream: the alpha partials of the fused
-    // epilogue are identical records
-    const int per = (nblocks + 7) >> 3;
-    const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
-    if (lmap >= nblocks)
+    const int lmap = spmv_block_of_launch(nblocks);
+    if (lmap < 0)
         return;
     const int lb = epi.first_block + lmap;  // a launch may cover a sub-range of the row-blocks (comm / compute overlap)
     if (EPI && epi.status && *epi.status != 0)
@@ -213,8 +213,7 @@ __global__ __launch_bounds__(256) void k_spmv_dia(DiaArgs da, const double* __re
     const int64_t row0 = int64_t(lb) * 256;
     const int nr = int(min(int64_t(256), nrows - row0));
     const int64_t r = row0 + min(tid, nr - 1);  // threads past the last row repeat it (their result is dropped)
-    int64_t vstride;
-    const double* vrow = dia_row(da, lb, min(tid, nr - 1), vstride);
+    const double* vrow = da.dia + int64_t(lb) * da.nd * 256 + min(tid, nr - 1);
     const int64_t grow = da.row_begin + r;
     double acc = 0.0;
     for (int g = 0; g < da.nd; g += kDiaGroup)
@@ -224,7 +223,7 @@ __global__ __launch_bounds__(256) void k_spmv_dia(DiaArgs da, const double* __re
         for (int u = 0; u < kDiaGroup; u++)
         {
             const int d = min(g + u, da.nd - 1);
-            v[u] = __builtin_nontemporal_load(vrow + int64_t(d) * vstride);  // read once per SpMV
+            v[u] = __builtin_nontemporal_load(vrow + int64_t(d) * 256);  // read once per SpMV
             const int64_t c = grow + off_s[d];
             xv[u] = x[min(max(c, int64_t(0)), int64_t(da.col_max))];  // out of range only where the value is a padding zero
         }
@@ -269,34 +268,16 @@ __global__ __launch_bounds__(256) void k_spmv_dia_win(DiaArgs da, mispec_dia_win
     constexpr bool MIR = NG >= kDiaMir;
     constexpr int NV = (NG % kDiaMir) * kDiaGroup;
     const PlanRegs<MIR ? NV : 1> pl(da.plan);
-    const int per = (nblocks + 7) >> 3;
-    const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
-    if (lmap >= nblocks)
+    const int lmap = spmv_block_of_launch(nblocks);
+    if (lmap < 0)
         return;
     const int lb = epi.first_block + lmap;  // a launch may cover a sub-range of the row-blocks (comm / compute overlap)
     if (EPI && epi.status && *epi.status != 0)
         return;
     const int tid = threadIdx.x;
     double beta = 1.0;
-    if (POST)
-    {
-        // every block takes the same decision from the same beta; one thread records it (Lanczos.h:99-128 without the restart branch)
-        StepState* st = static_cast<StepState*>(epi.post_scale_state);
-        beta = st->beta;
-        const bool first = (lmap == 0 && tid == 0);
-        if (beta < epi.post_scale_eps_sqrt)
-        {
-            if (first)
-            {
-                st->status = kStepSmallBeta;
-                st->stop_step = epi.post_scale_step;
-                st->stop_count = 0;
-            }
-            return;
-        }
-        if (first)
-            st->subd[epi.post_scale_step - 1] = beta;
-    }
+    if (POST && !post_scaled_step_start(epi, lmap == 0 && tid == 0, beta))
+        return;
     const int64_t row0 = int64_t(lb) * 256;
     const int nr = int(min(int64_t(256), nrows - row0));
     double v[NV];
@@ -309,11 +290,10 @@ __global__ __launch_bounds__(256) void k_spmv_dia_win(DiaArgs da, mispec_dia_win
     }
     else
     {
-        int64_t vstride;
-        const double* vrow = dia_row(da, lb, min(tid, nr - 1), vstride);
+        const double* vrow = da.dia + int64_t(lb) * da.nd * 256 + min(tid, nr - 1);
 #pragma unroll
         for (int k = 0; k < NV; k++)
-            v[k] = __builtin_nontemporal_load(vrow + int64_t(min(k, da.nd - 1)) * vstride);
+            v[k] = __builtin_nontemporal_load(vrow + int64_t(min(k, da.nd - 1)) * 256);
     }
     // The epilogue's operands travel with the matrix values: issued here, they are in flight during the window staging and
     // the barrier instead of costing the block a second round trip to HBM after its row sums (the kernel is bound by the
@@ -414,7 +394,7 @@ __global__ __launch_bounds__(256) void k_spmv_dia_win(DiaArgs da, mispec_dia_win
 // the 16-byte rate: it moved 1.38 GB at 5.5 TB/s where the 16-byte kernels of this library reach 5.8-6.3) — rows 2t and 2t + 1,
 // y / v_prev / v as 16-byte accesses too.  Same products in the same order, and the alpha record of the block is formed by the
 // same tree as everywhere else (per-row contributions through LDS, then the four 64-row shuffle trees and (w0 + w1) + (w2 + w3)):
-// bit-identical results and records.  Needs the block layout of the values (dia_row: ld == 0) and 16-byte aligned y / v vectors.
+// bit-identical results and records.  Needs 16-byte aligned y / v vectors.
 template <bool EPI, int NG, int NCW = 8, bool POST = false>
 __global__ __launch_bounds__(128) void k_spmv_dia_win2(DiaArgs da, mispec_dia_windows w, const double* __restrict__ x,
                                                        double* __restrict__ y, int64_t nrows, int nblocks, SpmvEpilogue epi)
@@ -424,33 +404,16 @@ __global__ __launch_bounds__(128) void k_spmv_dia_win2(DiaArgs da, mispec_dia_wi
     constexpr bool MIR = NG >= kDiaMir;
     constexpr int NV = (NG % kDiaMir) * kDiaGroup;
     const PlanRegs<MIR ? NV : 1> pl(da.plan);
-    const int per = (nblocks + 7) >> 3;
-    const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
-    if (lmap >= nblocks)
+    const int lmap = spmv_block_of_launch(nblocks);
+    if (lmap < 0)
         return;
     const int lb = epi.first_block + lmap;
     if (EPI && epi.status && *epi.status != 0)
         return;
     const int tid = threadIdx.x;
     double beta = 1.0;
-    if (POST)
-    {
-        StepState* st = static_cast<StepState*>(epi.post_scale_state);
-        beta = st->beta;
-        const bool first = (lmap == 0 && tid == 0);
-        if (beta < epi.post_scale_eps_sqrt)
-        {
-            if (first)
-            {
-                st->status = kStepSmallBeta;
-                st->stop_step = epi.post_scale_step;
-                st->stop_count = 0;
-            }
-            return;
-        }
-        if (first)
-            st->subd[epi.post_scale_step - 1] = beta;
-    }
+    if (POST && !post_scaled_step_start(epi, lmap == 0 && tid == 0, beta))
+        return;
     const int64_t row0 = int64_t(lb) * 256;
     const int nr = int(min(int64_t(256), nrows - row0));
     const int r0 = 2 * tid;  // rows r0, r0 + 1 of the block (the value array is zero-padded to whole blocks)
@@ -645,7 +608,10 @@ mispec_dia_plan make_plan(const int32_t* offs, int nd, const int32_t* mirrored)
                 if (offs[j] == -offs[i])
                 {
                     pl.src[j] = pl.slot(j);  // read again by the mirrored diagonal: not nontemporal, its lines stay in L2
-                    pl.src[i] = pl.slot(j) + (kMirrorNontemporal ? mispec_dia_plan::kStream : 0);
+                    // mirrored reads, and the stored loads they come back to, are plain loads: nontemporal ones measured as a loss
+                    // on data that is read again, and nontemporal mirrored reads made no difference where they were tried (on the
+                    // 16-byte variant of dia_load2's odd case, profiles/r15b_bench_dia_sym_ab.jsonl)
+                    pl.src[i] = pl.slot(j);
                 }
     for (int i = nd; i < 32; i++)  // the kernels load whole groups of eight: the rest repeat the last diagonal
     {
@@ -702,7 +668,6 @@ void build_dia(mispec_csr& A, const std::vector<int32_t>& dict)
     }
     // the values of a 256-row block are stored as one contiguous [nd][256] piece, so a workgroup streams ONE 30 KB run instead
     // of nd runs of 2 KB that are 80 MB apart (the diagonal-major layout dia[k][row] of round 1 measured 1.5 % slower and is gone)
-    constexpr bool blocked = true;
     const int64_t ld = round_up(nloc, 256);
     DevBuf<int32_t> d_pos;
     DevBuf<int> d_bad;
@@ -715,8 +680,8 @@ void build_dia(mispec_csr& A, const std::vector<int32_t>& dict)
     MISPEC_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), st));
     MISPEC_HIP(hipMemcpyAsync(d_pos.p, pos.data(), pos.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     MISPEC_HIP(hipMemcpyAsync(A.dia_off.p, offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_build_dia, dim3(unsigned((nloc + 255) / 256)), dim3(256), 0, st, A.rowptr.p, A.codes.p, A.val.p, d_pos.p, nloc, ld,
-                       A.dia.p, d_bad.p, blocked ? nd : 0);
+    hipLaunchKernelGGL(k_build_dia, dim3(unsigned((nloc + 255) / 256)), dim3(256), 0, st, A.rowptr.p, A.codes.p, A.val.p, d_pos.p, nloc, nd,
+                       A.dia.p, d_bad.p);
     MISPEC_HIP(hipGetLastError());
     int bad = 0;
     MISPEC_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -727,7 +692,6 @@ void build_dia(mispec_csr& A, const std::vector<int32_t>& dict)
         A.dia_off.release();
         return;
     }
-    A.dia_ld = blocked ? 0 : ld;
     A.ndia = nd;
     // x windows: consecutive sorted offsets share a window while it stays within 256 + 256 entries
     mispec_dia_windows w;
@@ -804,180 +768,43 @@ void build_dia(mispec_csr& A, const std::vector<int32_t>& dict)
 
 void launch_spmv_dia(const mispec_csr& A, const SpmvLaunch& L)
 {
-    const dim3 grid = L.grid, block = L.block;
-    const int64_t nloc = L.nloc;
-    const int nblocks = L.nblocks;
-    const SpmvEpilogue* epi = L.epi;
-    const SpmvEpilogue e = L.e;
-    const hipEvent_t ev_start = L.ev_start, ev_stop = L.ev_stop;
-    const double* x_dev = L.x_dev;
-    double* y_dev = L.y_dev;
-        const DiaArgs da{A.dia.p, A.dia_off.p, A.dia_ld, A.ndia, int(A.n_cols - 1), A.row_begin, A.dia_plan};
-        // with mirrored diagonals the instantiations that read the plan (NG + kDiaMir): they know the block layout only
-        const bool mir = A.dia_plan.nstored != A.ndia;
-        MISPEC_REQUIRE(!mir || (A.dia_ld == 0 && A.dia_win.nc > 0), "diagonal storage: a mirror plan needs the block layout and x windows");
-        // x staged through LDS windows when the offsets form at most 8 clusters, else direct loads (k_spmv_dia)
-        // two rows per thread with 16-byte loads (k_spmv_dia_win2) when the layout and the alignment allow
-        const bool dia2 = A.dia_win.nc > 0 && A.dia_ld == 0 && A.ndia <= 2 * kDiaGroup &&
-                          (reinterpret_cast<uintptr_t>(y_dev) & 15) == 0 &&
-                          (!epi || ((reinterpret_cast<uintptr_t>(e.v_rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(e.v_prev) & 15) == 0));
-        if (dia2)
-        {
-            const size_t lds2 = size_t(A.dia_win.total + 256) * sizeof(double);
-            const dim3 block2(128);
-            const int ng = (A.ndia + kDiaGroup - 1) / kDiaGroup;
-            const bool post = epi && e.post_scale_state;
-#define MISPEC_DIA2_LAUNCH(E, G, W, P)                                                                                                  \
-    do                                                                                                                                  \
-    {                                                                                                                                   \
-        if (ev_start && ev_stop)                                                                                                        \
-            hipExtLaunchKernelGGL((k_spmv_dia_win2<E, G, W, P>), grid, block2, lds2, A.ctx->stream, ev_start, ev_stop, 0, da, A.dia_win, \
-                                  x_dev, y_dev, nloc, nblocks, e);                                                                      \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((k_spmv_dia_win2<E, G, W, P>), grid, block2, lds2, A.ctx->stream, da, A.dia_win, x_dev, y_dev, nloc,     \
-                               nblocks, e);                                                                                             \
-    } while (0)
-#define MISPEC_DIA2_W(E, G, P)               \
-    do                                       \
-    {                                        \
-        if (A.dia_win.nc <= 4)               \
-            MISPEC_DIA2_LAUNCH(E, G, 4, P);  \
-        else if (A.dia_win.nc <= 6)          \
-            MISPEC_DIA2_LAUNCH(E, G, 6, P);  \
-        else                                 \
-            MISPEC_DIA2_LAUNCH(E, G, 8, P);  \
-    } while (0)
-#define MISPEC_DIA2_G(E, P)          \
-    do                               \
-    {                                \
-        if (ng == 1 && !mir)                   \
-            MISPEC_DIA2_W(E, 1, P);            \
-        else if (!mir)                         \
-            MISPEC_DIA2_W(E, 2, P);            \
-        else if (ng == 1)                      \
-            MISPEC_DIA2_W(E, kDiaMir + 1, P);  \
-        else                                   \
-            MISPEC_DIA2_W(E, kDiaMir + 2, P);  \
-    } while (0)
-            if (post)
-                MISPEC_DIA2_G(true, true);
-            else if (epi)
-                MISPEC_DIA2_G(true, false);
-            else
-                MISPEC_DIA2_G(false, false);
-#undef MISPEC_DIA2_G
-#undef MISPEC_DIA2_W
-#undef MISPEC_DIA2_LAUNCH
-            MISPEC_HIP(hipGetLastError());
-            return;
-        }
-        if (A.dia_win.nc > 0)
-        {
-            const size_t lds = size_t(A.dia_win.total) * sizeof(double);
-            const int ng = (A.ndia + kDiaGroup - 1) / kDiaGroup + (mir ? kDiaMir : 0);
-#define MISPEC_DIA_WIN_W(E, G, W)                                                                                             \
-    do                                                                                                                     \
-    {                                                                                                                      \
-        if (ev_start && ev_stop)                                                                                           \
-            hipExtLaunchKernelGGL((k_spmv_dia_win<E, G, W>), grid, block, lds, A.ctx->stream, ev_start, ev_stop, 0, da, A.dia_win, x_dev, \
-                                  y_dev, nloc, nblocks, e);                                                                \
-        else                                                                                                               \
-            hipLaunchKernelGGL((k_spmv_dia_win<E, G, W>), grid, block, lds, A.ctx->stream, da, A.dia_win, x_dev, y_dev, nloc, nblocks, e); \
-    } while (0)
-#define MISPEC_DIA_WIN(E, G)              \
-    do                                    \
-    {                                     \
-        if (A.dia_win.nc <= 4)            \
-            MISPEC_DIA_WIN_W(E, G, 4);    \
-        else if (A.dia_win.nc <= 6)       \
-            MISPEC_DIA_WIN_W(E, G, 6);    \
-        else                              \
-            MISPEC_DIA_WIN_W(E, G, 8);    \
-    } while (0)
-#define MISPEC_DIA_WIN_G(E)          \
-    do                               \
-    {                                \
-        if (ng == 1)                           \
-            MISPEC_DIA_WIN(E, 1);              \
-        else if (ng == 2)                      \
-            MISPEC_DIA_WIN(E, 2);              \
-        else if (ng == 3)                      \
-            MISPEC_DIA_WIN(E, 3);              \
-        else if (ng == 4)                      \
-            MISPEC_DIA_WIN(E, 4);              \
-        else if (ng == kDiaMir + 1)            \
-            MISPEC_DIA_WIN(E, kDiaMir + 1);    \
-        else if (ng == kDiaMir + 2)            \
-            MISPEC_DIA_WIN(E, kDiaMir + 2);    \
-        else if (ng == kDiaMir + 3)            \
-            MISPEC_DIA_WIN(E, kDiaMir + 3);    \
-        else                                   \
-            MISPEC_DIA_WIN(E, kDiaMir + 4);    \
-    } while (0)
-            if (epi && e.post_scale_state)
-            {
-#define MISPEC_DIA_WIN_POST_W(G, W)                                                                                                    \
-    do                                                                                                                                 \
-    {                                                                                                                                  \
-        if (ev_start && ev_stop)                                                                                                       \
-            hipExtLaunchKernelGGL((k_spmv_dia_win<true, G, W, true>), grid, block, lds, A.ctx->stream, ev_start, ev_stop, 0, da, A.dia_win, \
-                                  x_dev, y_dev, nloc, nblocks, e);                                                                     \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((k_spmv_dia_win<true, G, W, true>), grid, block, lds, A.ctx->stream, da, A.dia_win, x_dev, y_dev, nloc, \
-                               nblocks, e);                                                                                            \
-    } while (0)
-#define MISPEC_DIA_WIN_POST(G)               \
-    do                                       \
-    {                                        \
-        if (A.dia_win.nc <= 4)               \
-            MISPEC_DIA_WIN_POST_W(G, 4);     \
-        else if (A.dia_win.nc <= 6)          \
-            MISPEC_DIA_WIN_POST_W(G, 6);     \
-        else                                 \
-            MISPEC_DIA_WIN_POST_W(G, 8);     \
-    } while (0)
-                if (ng == 1)
-                    MISPEC_DIA_WIN_POST(1);
-                else if (ng == 2)
-                    MISPEC_DIA_WIN_POST(2);
-                else if (ng == 3)
-                    MISPEC_DIA_WIN_POST(3);
-                else if (ng == 4)
-                    MISPEC_DIA_WIN_POST(4);
-                else if (ng == kDiaMir + 1)
-                    MISPEC_DIA_WIN_POST(kDiaMir + 1);
-                else if (ng == kDiaMir + 2)
-                    MISPEC_DIA_WIN_POST(kDiaMir + 2);
-                else if (ng == kDiaMir + 3)
-                    MISPEC_DIA_WIN_POST(kDiaMir + 3);
-                else
-                    MISPEC_DIA_WIN_POST(kDiaMir + 4);
-#undef MISPEC_DIA_WIN_POST
-#undef MISPEC_DIA_WIN_POST_W
-            }
-            else if (epi)
-                MISPEC_DIA_WIN_G(true);
-            else
-                MISPEC_DIA_WIN_G(false);
-#undef MISPEC_DIA_WIN_G
-#undef MISPEC_DIA_WIN
-#undef MISPEC_DIA_WIN_W
-            MISPEC_HIP(hipGetLastError());
-            return;
-        }
-        if (ev_start && ev_stop)
-        {
-            if (epi)
-                hipExtLaunchKernelGGL(k_spmv_dia<true>, grid, block, 0, A.ctx->stream, ev_start, ev_stop, 0, da, x_dev, y_dev, nloc, nblocks, e);
-            else
-                hipExtLaunchKernelGGL(k_spmv_dia<false>, grid, block, 0, A.ctx->stream, ev_start, ev_stop, 0, da, x_dev, y_dev, nloc, nblocks, e);
-        }
-        else if (epi)
-            hipLaunchKernelGGL(k_spmv_dia<true>, grid, block, 0, A.ctx->stream, da, x_dev, y_dev, nloc, nblocks, e);
-        else
-            hipLaunchKernelGGL(k_spmv_dia<false>, grid, block, 0, A.ctx->stream, da, x_dev, y_dev, nloc, nblocks, e);
+    const DiaArgs da{A.dia.p, A.dia_off.p, A.ndia, int(A.n_cols - 1), A.row_begin, A.dia_plan};
+    // with mirrored diagonals the instantiations that read the plan (NG + kDiaMir)
+    const bool mir = A.dia_plan.nstored != A.ndia;
+    MISPEC_REQUIRE(!mir || A.dia_win.nc > 0, "diagonal storage: a mirror plan needs x windows");
+    const int ng = (A.ndia + kDiaGroup - 1) / kDiaGroup + (mir ? kDiaMir : 0);
+    const bool post = L.epi && L.e.post_scale_state;
+    const auto launch = [&](auto kernel, dim3 block, size_t lds, const auto&... operands) {
+        launch_kernel(kernel, L.grid, block, lds, A.ctx->stream, L.ev_start, L.ev_stop, da, operands..., L.x_dev, L.y_dev, L.nloc,
+                      L.nblocks, L.e);
         MISPEC_HIP(hipGetLastError());
+    };
+    // x staged through LDS windows when the offsets form at most 8 clusters, else direct loads (k_spmv_dia)
+    if (A.dia_win.nc == 0)
+    {
+        with_bool(L.epi != nullptr, [&](auto E) { launch(k_spmv_dia<E()>, L.block, 0); });
         return;
+    }
+    // two rows per thread with 16-byte loads (k_spmv_dia_win2) when the number of diagonals and the alignment allow
+    const auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool dia2 = A.ndia <= 2 * kDiaGroup && aligned16(L.y_dev) && (!L.epi || (aligned16(L.e.v_rows) && aligned16(L.e.v_prev)));
+    with_bool(L.epi != nullptr, [&](auto E) {
+        with_bool(post, [&](auto P) {
+            with_tier<4, 6, 8>(A.dia_win.nc, [&](auto W) {
+                if constexpr (E() || !P())  // POST only with EPI
+                {
+                    if (dia2)
+                        with_tier<1, 2, kDiaMir + 1, kDiaMir + 2>(ng, [&](auto G) {
+                            launch(k_spmv_dia_win2<E(), G(), W(), P()>, dim3(128), size_t(A.dia_win.total + 256) * sizeof(double), A.dia_win);
+                        });
+                    else
+                        with_tier<1, 2, 3, 4, kDiaMir + 1, kDiaMir + 2, kDiaMir + 3, kDiaMir + 4>(ng, [&](auto G) {
+                            launch(k_spmv_dia_win<E(), G(), W(), P()>, L.block, size_t(A.dia_win.total) * sizeof(double), A.dia_win);
+                        });
+                }
+            });
+        });
+    });
 }
 
 }  // namespace mispec

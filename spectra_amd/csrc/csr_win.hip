@@ -324,9 +324,8 @@ __global__ __launch_bounds__(256) void k_spmv_csr_win(const int32_t* __restrict_
     double* const xs = smem_win + kCap + 4;    // the block's windows of x
     __shared__ double red[4];
 
-    const int per = (nblocks + 7) >> 3;
-    const int lmap = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
-    if (lmap >= nblocks)
+    const int lmap = spmv_block_of_launch(nblocks);
+    if (lmap < 0)
         return;
     const int lb = epi.first_block + lmap;
     if (EPI && epi.status && *epi.status != 0)
@@ -578,67 +577,28 @@ void build_windows(mispec_csr& A)
 
 void launch_spmv_csr_win(const mispec_csr& A, const SpmvLaunch& L)
 {
-    const dim3 grid = L.grid, block = L.block;
-    const int64_t nloc = L.nloc;
-    const int nblocks = L.nblocks;
-    const SpmvEpilogue* epi = L.epi;
-    const SpmvEpilogue e = L.e;
-    const hipEvent_t ev_start = L.ev_start, ev_stop = L.ev_stop;
-    const double* x_dev = L.x_dev;
-    double* y_dev = L.y_dev;
-        // measured in the solver loop (profiles/r09a, r09b): chunks of 1008 products with the next chunk's loads ahead — the
-        // smallest LDS footprint, most resident blocks — for up to 16 entries per row (M-band 0.372 -> 0.369 ms, jittered band
-        // 0.412 -> 0.368 ms against the gather kernel on the same box); longer rows take larger chunks (fewer barrier rounds):
-        // 2032 products with the loads ahead, 4080 without (two chunks of registers would not fit)
-        int iters = double(A.nnz) <= 16.0 * double(nloc) ? 1 : (double(A.nnz) <= 32.0 * double(nloc) ? 2 : 4);
-        // (64 bytes of margin: the kernel's static `red[4]` shares the 64 KiB with the dynamic allocation — ADVICE r05)
-        while (iters > 1 && size_t(chunk_cap(256) - (4 - iters) * 1024 + 4 + A.win_lds_doubles) * sizeof(double) > 65536 - 64)
-            iters >>= 1;  // products + windows within the 64 KiB a launch gets without an attribute
-        const int xi = (A.win_lds_doubles + 511) / 512;
-        const int cap = chunk_cap(256) - (4 - iters) * 1024;
-        const size_t lds = size_t(cap + 4 + A.win_lds_doubles) * sizeof(double);
-        const int col_max = int(A.n_cols - 1);
-#define MISPEC_WIN_LAUNCH(E, I, X, P)                                                                                             \
-    do                                                                                                                             \
-    {                                                                                                                              \
-        if (ev_start && ev_stop)                                                                                                   \
-            hipExtLaunchKernelGGL((k_spmv_csr_win<E, I, X, P>), grid, block, lds, A.ctx->stream, ev_start, ev_stop, 0, A.rowptr.p,  \
-                                  A.colind.p, A.val.p, x_dev, y_dev, nloc, nblocks, e, A.wtab.p, col_max);                          \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((k_spmv_csr_win<E, I, X, P>), grid, block, lds, A.ctx->stream, A.rowptr.p, A.colind.p, A.val.p,     \
-                               x_dev, y_dev, nloc, nblocks, e, A.wtab.p, col_max);                                                 \
-    } while (0)
-#define MISPEC_WIN_X(E, I, P)              \
-    do                                     \
-    {                                      \
-        if (xi <= 3)                       \
-            MISPEC_WIN_LAUNCH(E, I, 3, P); \
-        else if (xi <= 5)                  \
-            MISPEC_WIN_LAUNCH(E, I, 5, P); \
-        else if (xi <= 8)                  \
-            MISPEC_WIN_LAUNCH(E, I, 8, P); \
-        else                               \
-            MISPEC_WIN_LAUNCH(E, I, 12, P); \
-    } while (0)
-#define MISPEC_WIN(E)                 \
-    do                                \
-    {                                 \
-        if (iters == 1)               \
-            MISPEC_WIN_X(E, 1, true); \
-        else if (iters == 2)          \
-            MISPEC_WIN_X(E, 2, true); \
-        else                          \
-            MISPEC_WIN_X(E, 4, false); \
-    } while (0)
-        if (epi)
-            MISPEC_WIN(true);
-        else
-            MISPEC_WIN(false);
-#undef MISPEC_WIN
-#undef MISPEC_WIN_X
-#undef MISPEC_WIN_LAUNCH
-        MISPEC_HIP(hipGetLastError());
-        return;
+    // measured in the solver loop (profiles/r09a, r09b): chunks of 1008 products with the next chunk's loads ahead — the
+    // smallest LDS footprint, most resident blocks — for up to 16 entries per row (M-band 0.372 -> 0.369 ms, jittered band
+    // 0.412 -> 0.368 ms against the gather kernel on the same box); longer rows take larger chunks (fewer barrier rounds):
+    // 2032 products with the loads ahead, 4080 without (two chunks of registers would not fit)
+    int iters = double(A.nnz) <= 16.0 * double(L.nloc) ? 1 : (double(A.nnz) <= 32.0 * double(L.nloc) ? 2 : 4);
+    // (64 bytes of margin: the kernel's static `red[4]` shares the 64 KiB with the dynamic allocation — ADVICE r05)
+    while (iters > 1 && size_t(chunk_cap(256) - (4 - iters) * 1024 + 4 + A.win_lds_doubles) * sizeof(double) > 65536 - 64)
+        iters >>= 1;  // products + windows within the 64 KiB a launch gets without an attribute
+    const int xi = (A.win_lds_doubles + 511) / 512;
+    const int cap = chunk_cap(256) - (4 - iters) * 1024;
+    const size_t lds = size_t(cap + 4 + A.win_lds_doubles) * sizeof(double);
+    const int col_max = int(A.n_cols - 1);
+    with_bool(L.epi != nullptr, [&](auto E) {
+        with_tier<1, 2, 4>(iters, [&](auto I) {
+            with_tier<3, 5, 8, 12>(xi, [&](auto X) {
+                constexpr bool PF = I() < 4;  // the next chunk's loads ahead: (ITERS, PF) = (1, true), (2, true), (4, false)
+                launch_kernel(k_spmv_csr_win<E(), I(), X(), PF>, L.grid, L.block, lds, A.ctx->stream, L.ev_start, L.ev_stop, A.rowptr.p,
+                              A.colind.p, A.val.p, L.x_dev, L.y_dev, L.nloc, L.nblocks, L.e, A.wtab.p, col_max);
+            });
+        });
+    });
+    MISPEC_HIP(hipGetLastError());
 }
 
 }  // namespace mispec

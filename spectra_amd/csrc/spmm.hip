@@ -64,11 +64,8 @@ __global__ __launch_bounds__(kSpmmThreads) void k_spmm_csr(const int32_t* __rest
     __shared__ __attribute__((aligned(16))) double s_val[kSpmmCap + 4];
     __shared__ __attribute__((aligned(16))) int32_t s_col[kSpmmCap + 4];
 
-    // XCD-aware map (k_spmv_csr_stream): gridDim.x == 8 * per; block b runs on XCD b % 8 and takes the (b/8)-th row-block of
-    // that XCD's contiguous range
-    const int per = (nblocks + 7) >> 3;
-    const int lb = (int(blockIdx.x) & 7) * per + (int(blockIdx.x) >> 3);
-    if (lb >= nblocks)
+    const int lb = spmv_block_of_launch(nblocks);
+    if (lb < 0)
         return;
 
     const int tid = threadIdx.x;
@@ -177,13 +174,12 @@ void launch_panel(const mispec_csr& A, const double* X, int64_t ldx, double* Y, 
 {
     const int64_t nloc = A.local_rows();
     const int nblocks = spmv_num_blocks(nloc);
-    const int per = (nblocks + 7) >> 3;
     hipStream_t st = A.ctx->stream;
     if (A.n_cols > 0)
         hipLaunchKernelGGL((k_spmm_pack<KB>), dim3(unsigned((A.n_cols + 255) / 256)), dim3(256), 0, st, A.n_cols, A.perm.p, X, ldx,
                            A.spmm_x.p);
     MISPEC_HIP(hipGetLastError());
-    hipLaunchKernelGGL((k_spmm_csr<KB>), dim3(unsigned(per * 8)), dim3(kSpmmThreads), 0, st, A.rowptr.p, A.colind.p, A.val.p,
+    hipLaunchKernelGGL((k_spmm_csr<KB>), dim3(spmv_grid_blocks(nblocks)), dim3(kSpmmThreads), 0, st, A.rowptr.p, A.colind.p, A.val.p,
                        A.spmm_x.p, A.perm.p, Y, ldy, nloc, nblocks);
     MISPEC_HIP(hipGetLastError());
 }

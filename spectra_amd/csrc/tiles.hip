@@ -28,7 +28,7 @@
 // block, hence tiles of ~25-200 entries and a different second phase) would lift it.  The two-phase variants (2.38 / 2.11 ms
 // in total) were removed again.
 #include "tiles.hpp"
-#include "csr.hpp"
+#include "csr_kernels.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -423,21 +423,10 @@ void launch_spmv_tiles(const DevTiles& T, hipStream_t stream, const double* x, d
 {
     const SpmvEpilogue e = epi ? *epi : SpmvEpilogue{};
     const dim3 grid(static_cast<unsigned>(T.nseg)), block(kTileThreads);
-#define MISPEC_TILES(E)                                                                                                     \
-    do                                                                                                                      \
-    {                                                                                                                       \
-        if (ev_start && ev_stop)                                                                                            \
-            hipExtLaunchKernelGGL((k_spmv_tiles<E>), grid, block, 0, stream, ev_start, ev_stop, 0, T.seg_entry.p, T.seg_chunk.p, \
-                                  T.chunks.p, T.val.p, T.idx.p, x, y, nrows, nblocks256, int(T.nseg), e);                  \
-        else                                                                                                                \
-            hipLaunchKernelGGL((k_spmv_tiles<E>), grid, block, 0, stream, T.seg_entry.p, T.seg_chunk.p, T.chunks.p, T.val.p, \
-                               T.idx.p, x, y, nrows, nblocks256, int(T.nseg), e);                                          \
-    } while (0)
-    if (epi)
-        MISPEC_TILES(true);
-    else
-        MISPEC_TILES(false);
-#undef MISPEC_TILES
+    with_bool(epi != nullptr, [&](auto E) {
+        launch_kernel(k_spmv_tiles<E()>, grid, block, 0, stream, ev_start, ev_stop, T.seg_entry.p, T.seg_chunk.p, T.chunks.p, T.val.p,
+                      T.idx.p, x, y, nrows, nblocks256, int(T.nseg), e);
+    });
     MISPEC_HIP(hipGetLastError());
 }
 

@@ -25,7 +25,13 @@ SHAPES = [
     (1500, (1, 2, 3, 1499)),                            # k almost n WITH diagonal storage (9 diagonals, 0.78 full): nearly every
                                                         # row of the mirrored -1499 reads the zero lead
     (N_HEADLINE, HEADLINE),                             # the headline pattern, far diagonals included
+    (256 * 8 + 37, (1, 300, 600, 900)),                 # 9 diagonals in 7 clusters: 8 registers of window entries (NCW = 8), even
+                                                        # and odd shifts
+    (256 * 40 + 37, (1, 2, 3, 500, 501, 502, 503, 2000, 2001, 2002)),  # 21 diagonals, 5 clusters: one row per thread, 3 groups,
+                                                        # plain (setting 0) and mirrored
+    (1000, tuple(range(1, 16))),                        # 31 diagonals in one cluster: 4 groups, plain and mirrored
 ]
+SEVEN_CLUSTERS, THREE_GROUPS = SHAPES[6], SHAPES[7]
 
 
 def build(make, setting):
@@ -86,11 +92,11 @@ def test_counts_through_dia_info(ctx):
 
 
 @pytest.mark.parametrize("setting", SETTINGS)
-def test_unaligned_operands(ctx, setting):
-    """y eight bytes off a 16-byte boundary: the one-row-per-thread kernel k_spmv_dia_win runs."""
+@pytest.mark.parametrize("n,offsets", [SHAPES[2], SEVEN_CLUSTERS], ids=["5clusters", "7clusters"])
+def test_unaligned_operands(ctx, n, offsets, setting):
+    """y eight bytes off a 16-byte boundary: the one-row-per-thread kernel k_spmv_dia_win runs (NCW = 6 and 8)."""
     import torch
 
-    n, offsets = SHAPES[2]
     op = build(lambda: sa.SparseSymMatProd.synth_band(n, offsets=offsets, ctx=ctx), setting)
     xh = seeded(n)
     ref, aligned = products(op, xh)
@@ -165,14 +171,16 @@ def test_falling_back(ctx):
     assert np.array_equal(bits(got), bits(ref))
 
 
-@pytest.mark.parametrize("orth", ["onesweep", "reference"])
-def test_in_the_solver(ctx, orth):
-    """Both fused instantiations (the post-scaled one of the one-sweep steps, the plain one of the reference flow) and their
-    epilogue records: a solve does not change by a bit."""
+@pytest.mark.parametrize("orth", ["onesweep", "reference", "onesweep-twored"])
+@pytest.mark.parametrize("n,offsets", [(N_HEADLINE, HEADLINE), THREE_GROUPS], ids=["headline", "21diagonals"])
+def test_in_the_solver(ctx, n, offsets, orth):
+    """Both fused instantiations (the post-scaled one of the one-sweep steps — with onesweep-twored on every step, not only the
+    first of a run — and the plain one of the reference flow) and their epilogue records, two rows per thread (headline) and one
+    row per thread with three groups (21 diagonals): a solve does not change by a bit."""
     runs = {}
     for setting in ("0", "all"):
-        op = build(lambda: sa.SparseSymMatProd.synth_band(N_HEADLINE, offsets=HEADLINE, ctx=ctx), setting)
-        assert op.spmv_format() == 2 and op.dia_info()["nmirrored"] == (7 if setting == "all" else 0)
+        op = build(lambda: sa.SparseSymMatProd.synth_band(n, offsets=offsets, ctx=ctx), setting)
+        assert op.spmv_format() == 2 and op.dia_info()["nmirrored"] == (len(offsets) if setting == "all" else 0)
         eigs = sa.SymEigsSolver(op, 6, 16)
         eigs.set_orth_mode(orth)
         eigs.init()

@@ -291,6 +291,18 @@ def test_fused_epilogue_is_identical_in_every_storage_format():
         res.append((eigs.eigenvalues(), eigs.num_operations()))
     for ev, nops in res[1:]:
         assert np.array_equal(ev, res[0][0]) and nops == res[0][1]
+    # a band in 31 clusters (more than 8: no x windows, fill 0.77): the epilogue of the direct kernel k_spmv_dia<true>
+    wide = []
+    for fmt in (0, 2):
+        op = sa.SparseSymMatProd.synth_band(256 * 40 + 37, offsets=tuple(300 * k for k in range(1, 16)))
+        op.set_spmv_format(fmt)
+        assert op.spmv_format() == fmt
+        eigs = sa.SymEigsSolver(op, 6, 20)
+        eigs.set_orth_mode("reference")
+        eigs.init()
+        eigs.compute(sa.SortRule.LargestMagn, tol=1e-11)
+        wide.append((eigs.eigenvalues(), eigs.num_operations()))
+    assert np.array_equal(wide[0][0], wide[1][0]) and wide[0][1] == wide[1][1]
     one = []
     for fmt in (0, 1, 2):
         op = sa.SparseSymMatProd.synth_band(n)
