@@ -5,7 +5,7 @@
  * built in rounds 1-2 and are kept working, but they are not part of the thin shim the hot path
  * needs: include/mispec.h alone is that shim.
  * Where they live (round 6): the Davidson solver, the complex factorisation and the complex Hermitian
- * eigensolver (mispec_davidson_*, mispec_zdense_*, mispec_zcsr_*, mispec_zfac_*, mispec_hermeigs_*: their
+ * eigensolver and the LOBPCG solver (mispec_davidson_*, mispec_zdense_*, mispec_zcsr_*, mispec_zfac_*, mispec_hermeigs_*, mispec_lobpcg_*: their
  * own kernels, nothing in the real hot path calls them) are in a library of their own, spectra_amd/libmispec_extras.so, built on libmispec.so — link -lmispec_extras
  * -lmispec.  The dense operators and the shift variants share objects with the hot path (the dense
  * GEMV applies the last level of the banded shift solve) and stay in libmispec.so.
@@ -177,6 +177,55 @@ int64_t mispec_hermeigs_num_iterations(const mispec_hermeigs* S);
 int64_t mispec_hermeigs_num_operations(const mispec_hermeigs* S);
 int mispec_hermeigs_eigenvalues(const mispec_hermeigs* S, double* out_host, int64_t* count);
 int mispec_hermeigs_eigenvectors(const mispec_hermeigs* S, int64_t nvec, double* out_host, int64_t* ncols);
+
+/* ---------------------------------------------------------------------------
+ * LOBPCGSolver — replaces contrib/LOBPCGSolver.h: the m smallest (or largest) eigenpairs of the SPD pencil A x = lambda B x by the
+ * locally optimal block preconditioned conjugate gradient method, with an optional preconditioner (a sparse matrix T applied as
+ * R <- T R, or the Jacobi scaling by 1 / diag(A)), a warm start from an n x m block and constraints (deflation against known vectors).
+ * The blocks [X | R | P], their images under A and B and the constraints live in HBM; per iteration there is ONE block product with A
+ * on the active columns; the Gram matrices (order <= 63) are factored and the reduced eigenproblem is solved on the host.
+ * Limits (MISPEC_EINVAL): 1 <= m <= 21 and m < n; at most 21 constraints, m + c < n; A square and unsharded; B and T of A's shape;
+ * selection SmallestAlge (7) or LargestAlge (3).  Info: 0 Success, 1 NumericalIssue, 2 NoConvergence, 3 InvalidInput (before compute).
+ * After NumericalIssue the eigenvalues / vectors are those of the last completed iteration (a failure in the setup: the start vectors
+ * and their Rayleigh quotients).  Gram matrices are factored with pivots below 1e-8 refused, so a tolerance below the rounding level of
+ * a residual ends in NumericalIssue, not NoConvergence.
+ * ------------------------------------------------------------------------- */
+typedef struct mispec_lobpcg mispec_lobpcg;
+int mispec_lobpcg_create(mispec_ctx* ctx, const mispec_csr* A, int64_t m, mispec_lobpcg** out);
+int mispec_lobpcg_destroy(mispec_lobpcg* S);
+int mispec_lobpcg_set_B(mispec_lobpcg* S, const mispec_csr* B);              /* NULL: the standard problem again */
+int mispec_lobpcg_set_preconditioner(mispec_lobpcg* S, const mispec_csr* T); /* NULL: none */
+int mispec_lobpcg_set_jacobi(mispec_lobpcg* S, int on);                      /* needs a positive diagonal of A */
+int mispec_lobpcg_set_constraints(mispec_lobpcg* S, const double* Y_host, int64_t ld, int64_t c); /* n x c, column-major; c = 0: none */
+/* n x m column-major start block; without one the columns are SimpleRandom streams, seed j + 1 for column j */
+int mispec_lobpcg_set_initial(mispec_lobpcg* S, const double* X_host, int64_t ld);
+/* a column is converged when |A x - lambda B x|_2 < tol_abs; *nconv = converged columns (from the fresh products of the end) */
+int mispec_lobpcg_compute(mispec_lobpcg* S, int selection, int64_t maxit, double tol_abs, int64_t* nconv);
+int mispec_lobpcg_info(const mispec_lobpcg* S);
+int64_t mispec_lobpcg_num_iterations(const mispec_lobpcg* S);
+int64_t mispec_lobpcg_num_operations(const mispec_lobpcg* S); /* columns multiplied by A */
+int64_t mispec_lobpcg_num_retries(const mispec_lobpcg* S);    /* iterations whose Rayleigh-Ritz step was repeated without P */
+int mispec_lobpcg_eigenvalues(const mispec_lobpcg* S, double* out);                        /* m values */
+int mispec_lobpcg_eigenvectors(const mispec_lobpcg* S, double* out_host, int64_t ld);      /* n x m, B-orthonormal */
+int mispec_lobpcg_residuals(const mispec_lobpcg* S, double* out_host, int64_t ld);         /* A X - B X diag(lambda), n x m */
+int mispec_lobpcg_residual_norms(const mispec_lobpcg* S, double* out);                     /* m values */
+/* The solver's kernels alone, on device pointers (column-major blocks); enqueued on the context's stream, then synchronised.
+ * For tests and measurements, not for inner loops: every call allocates and frees its own scratch (16 MB of partial records in HBM and a
+ * pinned host buffer); the solver keeps one set per handle.
+ * gram: G = U'W, p x q column-major into G_host, 1 <= p, q <= 64; symmetric != 0 (p == q): only i <= j is computed and mirrored.
+ * resid: R[:, k] = (AX - lambda BX)[:, idx k] (times dinv[row] when dinv is given) for k < a, and norms2[j] = |AX_j - lambda_j BX_j|^2
+ * of the unscaled residual for every j < m <= 21.  block_sub: Z <- Z - Y C for Z n x q, Y n x c, C c x q column-major, q, c <= 21. */
+int mispec_lobpcg_gram(mispec_ctx* ctx, const double* U_dev, int64_t ldu, int p, const double* W_dev, int64_t ldw, int q, int64_t n,
+                       int symmetric, double* G_host);
+int mispec_lobpcg_resid(mispec_ctx* ctx, const double* AX_dev, const double* BX_dev, int64_t ld, int m, int64_t n, const double* lambda_host,
+                        const int* idx_host, int a, const double* dinv_dev_or_null, double* R_dev, int64_t ldr, double* norms2_host);
+int mispec_lobpcg_block_sub(mispec_ctx* ctx, double* Z_dev, int64_t ldz, int q, const double* Y_dev, int64_t ldy, int c, const double* C_host,
+                            int64_t n);
+/* average ms of `reps` back-to-back launches (both stages, no read-back) of which = 0: the Gram kernel on p columns of U and q of W;
+ * 1: the residual kernel on p columns of U (as AX) and W (as BX), the first q active, R_dev the output; 2: the V*Q combination
+ * R_dev[:, :q] = U[:, :p] Q of the Rayleigh-Ritz step (W_dev unused); benchmark helper */
+int mispec_lobpcg_kernel_time(mispec_ctx* ctx, int which, const double* U_dev, const double* W_dev, int64_t ld, int p, int q, int64_t n,
+                              double* R_dev, int reps, float* ms_per_launch);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,8 @@ from ._capi import MispecError, Profile, build_library, check, lib
 __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatProd", "SparseSymShiftSolve", "SymEigsSolver",
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
-           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "dia_sym_plan", "mirror_triangle_device"]
+           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "dia_sym_plan", "mirror_triangle_device",
+           "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -1253,6 +1254,166 @@ class DavidsonSymEigsSolver:
             lib().mispec_davidson_destroy(self.h)
         except Exception:
             pass
+
+
+class LOBPCGInfo(enum.IntEnum):
+    """The info values of contrib/LOBPCGSolver.h (Eigen::ComputationInfo)."""
+    Success = 0
+    NumericalIssue = 1
+    NoConvergence = 2
+    InvalidInput = 3
+
+
+class LOBPCGSolver:
+    """contrib/LOBPCGSolver.h on the device: the m smallest (or largest) eigenpairs of A x = lambda B x by LOBPCG.
+    op, B: SparseSymMatProd (unsharded); X0: dense n x m start block, or nev columns of SimpleRandom streams (seed j + 1);
+    preconditioner: a sparse device operator (SparseSymMatProd, or SparseGenMatProd) applied as R <- T R, or "jacobi" (1 / diag A); constraints: dense n x c block the
+    eigenvectors are kept B-orthogonal to.  1 <= m <= 21, m < n, c <= 21, m + c < n."""
+
+    def __init__(self, op, X0=None, nev=None, B=None, preconditioner=None, constraints=None):
+        if not isinstance(op, _DeviceMatrix) or (B is not None and not isinstance(B, _DeviceMatrix)):
+            raise TypeError("LOBPCGSolver: the operators must be SparseSymMatProd")
+        n = op.rows()
+        if X0 is not None:
+            X0 = np.asfortranarray(X0, dtype=np.float64)
+            if X0.ndim != 2 or X0.shape[0] != n:
+                raise ValueError("LOBPCGSolver: the start block must have n rows")
+            if nev is not None and int(nev) != X0.shape[1]:
+                raise ValueError("LOBPCGSolver: nev differs from the number of start vectors")
+            nev = X0.shape[1]
+        elif nev is None:
+            raise ValueError("LOBPCGSolver: give a start block X0 or the number of eigenpairs nev")
+        self.op, self.B, self.T = op, B, None  # keeps the operators alive
+        self.ctx = op.ctx
+        self.n, self.m = n, int(nev)
+        self.h = C.c_void_p()
+        check(lib().mispec_lobpcg_create(self.ctx.h, op.h, self.m, C.byref(self.h)))
+        if B is not None:
+            check(lib().mispec_lobpcg_set_B(self.h, B.h))
+        if isinstance(preconditioner, str):
+            if preconditioner != "jacobi":
+                raise ValueError("LOBPCGSolver: the preconditioner is a SparseSymMatProd or the string 'jacobi'")
+            check(lib().mispec_lobpcg_set_jacobi(self.h, 1))
+        elif preconditioner is not None:
+            if not isinstance(preconditioner, _DeviceMatrix):
+                raise TypeError("LOBPCGSolver: the preconditioner is a SparseSymMatProd or the string 'jacobi'")
+            self.T = preconditioner
+            check(lib().mispec_lobpcg_set_preconditioner(self.h, preconditioner.h))
+        if constraints is not None:
+            Y = np.asfortranarray(constraints, dtype=np.float64)
+            if Y.ndim != 2 or Y.shape[0] != n:
+                raise ValueError("LOBPCGSolver: the constraints must have n rows")
+            check(lib().mispec_lobpcg_set_constraints(self.h, _dp(Y), n, Y.shape[1]))
+        if X0 is not None:
+            check(lib().mispec_lobpcg_set_initial(self.h, _dp(X0), n))
+
+    def compute(self, selection=SortRule.SmallestAlge, maxit=100, tol=1e-8):
+        """tol is absolute: a column is converged when |A x - lambda B x|_2 < tol.  Returns the number of converged columns."""
+        nconv = C.c_int64()
+        check(lib().mispec_lobpcg_compute(self.h, int(selection), int(maxit), float(tol), C.byref(nconv)))
+        return nconv.value
+
+    def info(self):
+        return LOBPCGInfo(lib().mispec_lobpcg_info(self.h))
+
+    def num_iterations(self):
+        return lib().mispec_lobpcg_num_iterations(self.h)
+
+    def num_operations(self):
+        return lib().mispec_lobpcg_num_operations(self.h)
+
+    def num_retries(self):
+        """Iterations whose Rayleigh-Ritz step was repeated without the block P."""
+        return lib().mispec_lobpcg_num_retries(self.h)
+
+    def eigenvalues(self):
+        out = np.empty(self.m)
+        check(lib().mispec_lobpcg_eigenvalues(self.h, _dp(out)))
+        return out
+
+    def residual_norms(self):
+        out = np.empty(self.m)
+        check(lib().mispec_lobpcg_residual_norms(self.h, _dp(out)))
+        return out
+
+    def eigenvectors(self):
+        out = np.empty((self.n, self.m), order="F")
+        check(lib().mispec_lobpcg_eigenvectors(self.h, _dp(out), self.n))
+        return out
+
+    def residuals(self):
+        out = np.empty((self.n, self.m), order="F")
+        check(lib().mispec_lobpcg_residuals(self.h, _dp(out), self.n))
+        return out
+
+    def __del__(self):
+        try:
+            lib().mispec_lobpcg_destroy(self.h)
+        except Exception:
+            pass
+
+
+def _torch_block(t, name):
+    """(device address, leading dimension, columns) of a column-major block held as a float64 CUDA tensor of shape (columns, ld):
+    row j of the tensor is column j of the block (slices along the first dimension are blocks of the same buffer)."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError("%s: expected a 2-D float64 CUDA tensor of shape (columns, ld) with unit stride along ld" % name)
+    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else t.shape[1]), t.shape[0]
+
+
+def _torch_sync():
+    import torch
+
+    torch.cuda.current_stream().synchronize()  # the library reads on the context's stream
+
+
+def lobpcg_gram(U, W, n, symmetric=False, ctx=None):
+    """G = U[:, :n]' W[:, :n] by the LOBPCG solver's Gram kernel (mispec_lobpcg_gram): U, W torch blocks (see _torch_block) of p, q <= 64
+    columns, possibly overlapping parts of one buffer; returns the p x q numpy array."""
+    ctx = ctx or default_context()
+    up, ldu, p = _torch_block(U, "lobpcg_gram")
+    wp, ldw, q = _torch_block(W, "lobpcg_gram")
+    G = np.empty((p, q), order="F")
+    _torch_sync()
+    check(lib().mispec_lobpcg_gram(ctx.h, C.c_void_p(up), ldu, p, C.c_void_p(wp), ldw, q, int(n), int(bool(symmetric)), _dp(G)))
+    return G
+
+
+def lobpcg_resid(AX, BX, n, lam, idx, R=None, dinv=None, ctx=None):
+    """The solver's residual kernel (mispec_lobpcg_resid): R[k] <- (AX - lam BX)[idx k] (times dinv per row when given) for the active
+    columns idx, and returns |AX_j - lam_j BX_j|^2 of every column j."""
+    ctx = ctx or default_context()
+    ap, ld, m = _torch_block(AX, "lobpcg_resid")
+    bp, ldb, mb = _torch_block(BX, "lobpcg_resid")
+    if ldb != ld or mb != m:
+        raise ValueError("lobpcg_resid: AX and BX must have the same shape")
+    lam = _f64(lam)
+    idx = _i32(idx)
+    if lam.shape != (m,):
+        raise ValueError("lobpcg_resid: one lambda per column")
+    rp, ldr = (None, 0)
+    if R is not None:
+        rp, ldr, _ = _torch_block(R, "lobpcg_resid")
+    out = np.empty(m)
+    _torch_sync()
+    check(lib().mispec_lobpcg_resid(ctx.h, C.c_void_p(ap), C.c_void_p(bp), ld, m, int(n), _dp(lam), _ip(idx), int(idx.size),
+                                    C.c_void_p(dinv.data_ptr()) if dinv is not None else None, C.c_void_p(rp) if rp else None, ldr,
+                                    _dp(out)))
+    return out
+
+
+def lobpcg_block_sub(Z, Y, Cmat, n, ctx=None):
+    """Z[:, :n] <- Z - Y C in place by the solver's constraint kernel (mispec_lobpcg_block_sub): Z of q, Y of c columns, C c x q."""
+    ctx = ctx or default_context()
+    zp, ldz, q = _torch_block(Z, "lobpcg_block_sub")
+    yp, ldy, c = _torch_block(Y, "lobpcg_block_sub")
+    Cm = np.asfortranarray(Cmat, dtype=np.float64)
+    if Cm.shape != (c, q):
+        raise ValueError("lobpcg_block_sub: C must be c x q")
+    _torch_sync()
+    check(lib().mispec_lobpcg_block_sub(ctx.h, C.c_void_p(zp), ldz, q, C.c_void_p(yp), ldy, c, _dp(Cm), int(n)))
 
 
 class _GEigsCholeskyOp:

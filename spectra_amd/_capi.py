@@ -10,7 +10,7 @@ import subprocess
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libmispec.so")
 EXTRAS_LIB_PATH = os.path.join(_PKG, "libmispec_extras.so")  # Davidson solver, complex factorisation (mispec_extras.h)
-EXTRAS_PREFIXES = ("mispec_davidson_", "mispec_zdense_", "mispec_zfac_", "mispec_zcsr_", "mispec_hermeigs_")
+EXTRAS_PREFIXES = ("mispec_davidson_", "mispec_zdense_", "mispec_zfac_", "mispec_zcsr_", "mispec_hermeigs_", "mispec_lobpcg_")
 CSRC = os.path.join(_PKG, "csrc")
 
 MISPEC_OK, MISPEC_EINVAL, MISPEC_ELOGIC, MISPEC_ERUNTIME = 0, -1, -2, -3
@@ -174,6 +174,27 @@ SIGNATURES = {
     "mispec_hermeigs_num_operations": (C.c_int64, [_vp]),
     "mispec_hermeigs_eigenvalues": (C.c_int, [_vp, _dp, _lp]),
     "mispec_hermeigs_eigenvectors": (C.c_int, [_vp, C.c_int64, _dp, _lp]),
+    # LOBPCG solver and its kernels (mispec_extras.h)
+    "mispec_lobpcg_create": (C.c_int, [_vp, _vp, C.c_int64, _vpp]),
+    "mispec_lobpcg_destroy": (C.c_int, [_vp]),
+    "mispec_lobpcg_set_B": (C.c_int, [_vp, _vp]),
+    "mispec_lobpcg_set_preconditioner": (C.c_int, [_vp, _vp]),
+    "mispec_lobpcg_set_jacobi": (C.c_int, [_vp, C.c_int]),
+    "mispec_lobpcg_set_constraints": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64]),
+    "mispec_lobpcg_set_initial": (C.c_int, [_vp, _dp, C.c_int64]),
+    "mispec_lobpcg_compute": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_double, _lp]),
+    "mispec_lobpcg_info": (C.c_int, [_vp]),
+    "mispec_lobpcg_num_iterations": (C.c_int64, [_vp]),
+    "mispec_lobpcg_num_operations": (C.c_int64, [_vp]),
+    "mispec_lobpcg_num_retries": (C.c_int64, [_vp]),
+    "mispec_lobpcg_eigenvalues": (C.c_int, [_vp, _dp]),
+    "mispec_lobpcg_eigenvectors": (C.c_int, [_vp, _dp, C.c_int64]),
+    "mispec_lobpcg_residuals": (C.c_int, [_vp, _dp, C.c_int64]),
+    "mispec_lobpcg_residual_norms": (C.c_int, [_vp, _dp]),
+    "mispec_lobpcg_gram": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int, _dp]),
+    "mispec_lobpcg_resid": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int64, _dp, _ip, C.c_int, _vp, _vp, C.c_int64, _dp]),
+    "mispec_lobpcg_block_sub": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, _dp, C.c_int64]),
+    "mispec_lobpcg_kernel_time": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, C.c_int, C.POINTER(C.c_float)]),
     "mispec_dense_destroy": (C.c_int, [_vp]),
     "mispec_dense_rows": (C.c_int64, [_vp]),
     "mispec_dense_cols": (C.c_int64, [_vp]),

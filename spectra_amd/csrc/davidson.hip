@@ -19,8 +19,10 @@
 #include <Spectra/internal/SmallDense.h>
 
 #include "csr.hpp"
+#include "csr_diag.hpp"
 #include "dense.hpp"
 #include "krylov.hpp"
+#include "sym_eigen.hpp"
 
 using namespace mispec;
 
@@ -28,20 +30,6 @@ namespace {
 constexpr int kDavidsonMaxCols = 256;  // search-space columns held on the device (the projected problem is solved densely on the host)
 
 constexpr int kThreads = 256;
-
-__global__ __launch_bounds__(kThreads) void k_csr_diag(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
-                                                        const double* __restrict__ val, int64_t row_begin, int64_t nloc,
-                                                        double* __restrict__ diag)
-{
-    const int64_t r = int64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (r >= nloc)
-        return;
-    double d = 0.0;
-    for (int p = rowptr[r]; p < rowptr[r + 1]; p++)
-        if (colind[p] == row_begin + r)
-            d += val[p];
-    diag[r] = d;
-}
 
 __global__ __launch_bounds__(kThreads) void k_dense_diag(const double* __restrict__ a, int64_t ld, int64_t n, double* __restrict__ diag)
 {
@@ -69,71 +57,6 @@ __global__ __launch_bounds__(kThreads) void k_dpr_correction(const double* __res
 }
 
 dim3 blocks_for(int64_t n) { return dim3(unsigned((n + kThreads - 1) / kThreads)); }
-
-// All eigenpairs of the symmetric s x s matrix G (column-major, destroyed): evals[s], evecs s x s column-major.
-// Householder reduction to tridiagonal form with the transformation accumulated, then the implicit-shift QR of
-// internal/SmallDense.h applied to that accumulated matrix.  Returns false if the QR iteration did not converge.
-bool symmetric_eigen(int s, std::vector<double>& G, std::vector<double>& evals, std::vector<double>& evecs)
-{
-    auto g = [&](int i, int j) -> double& { return G[size_t(j) * s + i]; };
-    evecs.assign(size_t(s) * s, 0.0);
-    auto q = [&](int i, int j) -> double& { return evecs[size_t(j) * s + i]; };
-    for (int i = 0; i < s; i++)
-        q(i, i) = 1.0;
-    std::vector<double> v(static_cast<size_t>(s)), w(static_cast<size_t>(s));
-    for (int k = 0; k + 2 < s; k++)
-    {
-        double norm2 = 0.0;
-        for (int i = k + 1; i < s; i++)
-            norm2 += g(i, k) * g(i, k);
-        const double x0 = g(k + 1, k);
-        if (!(norm2 - x0 * x0 > 0.0))
-            continue;  // already tridiagonal in this column
-        const double alpha = x0 > 0.0 ? -std::sqrt(norm2) : std::sqrt(norm2);
-        std::fill(v.begin(), v.end(), 0.0);
-        for (int i = k + 1; i < s; i++)
-            v[size_t(i)] = g(i, k);
-        v[size_t(k) + 1] -= alpha;
-        double vn = 0.0;
-        for (int i = k + 1; i < s; i++)
-            vn += v[size_t(i)] * v[size_t(i)];
-        vn = std::sqrt(vn);
-        if (!(vn > 0.0))
-            continue;
-        for (int i = k + 1; i < s; i++)
-            v[size_t(i)] /= vn;
-        // G <- H G H with H = I - 2 v v':  w = G v ; K = v'w ; G -= 2 (v w' + w v') - 4 K v v'
-        for (int i = 0; i < s; i++)
-        {
-            double acc = 0.0;
-            for (int j = k + 1; j < s; j++)
-                acc += g(i, j) * v[size_t(j)];
-            w[size_t(i)] = acc;
-        }
-        double K = 0.0;
-        for (int i = k + 1; i < s; i++)
-            K += v[size_t(i)] * w[size_t(i)];
-        for (int j = 0; j < s; j++)
-            for (int i = 0; i < s; i++)
-                g(i, j) -= 2.0 * (v[size_t(i)] * w[size_t(j)] + w[size_t(i)] * v[size_t(j)]) - 4.0 * K * v[size_t(i)] * v[size_t(j)];
-        // Q <- Q H
-        for (int i = 0; i < s; i++)
-        {
-            double acc = 0.0;
-            for (int j = k + 1; j < s; j++)
-                acc += q(i, j) * v[size_t(j)];
-            for (int j = k + 1; j < s; j++)
-                q(i, j) -= 2.0 * acc * v[size_t(j)];
-        }
-    }
-    evals.resize(static_cast<size_t>(s));
-    std::vector<double> subd(static_cast<size_t>(std::max(s - 1, 1)), 0.0);
-    for (int i = 0; i < s; i++)
-        evals[size_t(i)] = g(i, i);
-    for (int i = 0; i + 1 < s; i++)
-        subd[size_t(i)] = 0.5 * (g(i + 1, i) + g(i, i + 1));
-    return small::tridiag_eigen(s, evals.data(), subd.data(), evecs.data(), s, small::Lanes{0, 1}) == 0;
-}
 
 }  // namespace
 
@@ -317,7 +240,7 @@ extern "C" int mispec_davidson_create(mispec_ctx* ctx, const mispec_csr* A, int6
         MISPEC_REQUIRE(A->ctx == ctx && A->n_rows == A->n_cols, "mispec_davidson_create: needs a square matrix of this context");
         auto S = make_solver(ctx, A->n_rows, nev, nvec_init, nvec_max);
         S->A = A;
-        hipLaunchKernelGGL(k_csr_diag, blocks_for(S->n), dim3(kThreads), 0, ctx->stream, A->rowptr.p, A->colind.p, A->val.p, A->row_begin,
+        hipLaunchKernelGGL(k_csr_diag, blocks_for(S->n), dim3(kCsrDiagThreads), 0, ctx->stream, A->rowptr.p, A->colind.p, A->val.p, A->row_begin,
                            S->n, S->diag.p);
         MISPEC_HIP(hipGetLastError());
         if (A->reordered())
