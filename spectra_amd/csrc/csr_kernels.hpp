@@ -1,8 +1,9 @@
 // Device helpers shared by the SpMV kernels of csr.hip (CSR-stream), csr_win.hip (int32 CSR with x windows) and csr_dia.hip
-// (diagonal storage): vector types, the LDS chunk sizes, the offset-code descriptor, the fixed-order block sum, the row-block map
-// of a launch and the host's launch helpers.  Internal.
+// (diagonal storage): vector types, the LDS chunk sizes, the offset-code descriptor, the row-block map of a launch and the host's
+// launch helpers; the fixed-order block sum comes from device_helpers.hpp.  Internal.
 #pragma once
 #include "csr.hpp"
+#include "device_helpers.hpp"
 #include "krylov.hpp"
 
 #include <hip/hip_runtime.h>
@@ -13,7 +14,6 @@
 
 namespace {
 
-typedef double v2d __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 // THREADS * 4 entries * 4 load steps = 16 * THREADS >= cap + 3 (k_spmv_csr_stream's ITERS = 4)
@@ -31,24 +31,6 @@ struct SpmvCodes
     int col_max;       // n_cols - 1
     int64_t row_begin; // global index of local row 0
 };
-
-__device__ __forceinline__ double wave_reduce_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// Deterministic 256-thread sum; every thread returns the total.
-__device__ __forceinline__ double block_reduce_sum(double v, double* red)
-{
-    v = wave_reduce_sum(v);
-    if ((threadIdx.x & 63) == 0)
-        red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // XCD-aware row-block map of an SpMV launch over nblocks row-blocks: the grid is spmv_grid_blocks(nblocks) = 8 * per workgroups;
 // hardware sends block b to XCD b % 8, so block b takes the (b / 8)-th row-block of that XCD's contiguous range of `per` and an

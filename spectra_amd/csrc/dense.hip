@@ -6,6 +6,7 @@
 // Kernel: one wavefront per row.  A lane streams 16-byte pieces of the row (four in flight), x comes from the L2
 // (it is read by every row), a shuffle tree finishes the dot product.  Bound: HBM, 8 bytes per matrix entry.
 #include "dense.hpp"
+#include "device_helpers.hpp"
 
 #include <cstring>
 #include <memory>
@@ -66,10 +67,7 @@ __global__ __launch_bounds__(kGemvThreads) void k_row_gemv(int64_t rows, int64_t
         for (; c < cols; c += 64)
             acc0 += a[c] * x[c];
     }
-    double acc = (acc0 + acc1) + (acc2 + acc3);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        acc += __shfl_down(acc, off, 64);
+    const double acc = wave_reduce_sum((acc0 + acc1) + (acc2 + acc3));
     if (lane == 0)
         y[r] = acc;
 }

@@ -13,7 +13,10 @@
 //
 // Algorithmic bytes (8*n per vector pass): VTF (ncol+1), RESID_VTF (ncol+2 reads... w, v_i is
 // one of the ncol columns, so ncol+1 reads + 1 write), CORRECT_VTF (ncol+1 reads + 1 write).
+#include "device_helpers.hpp"
 #include "krylov.hpp"
+#include "orth_launch.hpp"
+#include "orth_step.hpp"
 
 #include <cstdlib>
 #include <string>
@@ -22,43 +25,8 @@ using namespace mispec;
 
 namespace {
 
-typedef double v2d __attribute__((ext_vector_type(2)));
-
 constexpr int kThreads = 256;
 constexpr int kTileRows = 128;
-
-// 16-byte load of two rows of a basis column with the non-temporal hint (streamed once per pass)
-__device__ __forceinline__ double2 load_streamed(const double* p)
-{
-    const v2d t = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p));  // (plain loads: round 4, profiles/r07b — the solve 1.7 % slower)
-    double2 r;
-    r.x = t.x;
-    r.y = t.y;
-    return r;
-}
-
-__device__ __forceinline__ double wave_reduce_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_reduce_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double block_reduce_sum(double v, double* red)
-{
-    v = wave_reduce_sum(v);
-    if ((threadIdx.x & 63) == 0)
-        red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // R = row pairs per lane and tile: a tile is 128*R rows, and each wave reads R consecutive KiB of every
 // column it owns (longer contiguous runs per column stream).
@@ -408,31 +376,7 @@ __global__ __launch_bounds__(64 * NW) void k_orth_lagged(OrthArgs a)
             }
     }
 
-    double* rec = a.partials + blockIdx.x;
-#pragma unroll
-    for (int jj = 0; jj < MAXS; jj++)
-    {
-        const double s = wave_reduce_sum(acc[jj]);
-        const double c = wave_reduce_sum(chk[jj]);
-        const int j = w + NW * jj;
-        if (lane == 0 && j < a.ncol)
-        {
-            rec[int64_t(j) * a.pstride] = s;
-            rec[int64_t(a.ncol + 1 + j) * a.pstride] = c;
-        }
-    }
-    if (w == 0)
-    {
-        b2 = wave_reduce_sum(b2);
-        dvi = wave_reduce_sum(dvi);
-        mx = wave_reduce_max(mx);
-        if (lane == 0)
-        {
-            rec[int64_t(a.ncol) * a.pstride] = dvi;
-            rec[kSlotBeta2 * a.pstride] = b2;
-            rec[kSlotMaxAbs * a.pstride] = mx;
-        }
-    }
+    lagged_record<NW>(a, 0, a.ncol, w, lane, acc, chk, b2, dvi, mx);
 }
 
 // What the scalar tail of a lagged step reads from global memory, loaded in ONE round at the start of the reducing kernel (the
@@ -1486,119 +1430,56 @@ int persistent_grid(const mispec_ctx& ctx, int64_t work_items, int per_cu)
     return int(g);
 }
 
+// One instantiation per slot count (columns per wave, ceil(ncol / 4); 16 and more: 16): a wave then issues exactly the
+// loads it needs — with a coarser set of sizes the surplus slots re-read column 0 and spend L1/L2 bandwidth.
+// Up to 10 slots a tile is two row pairs per lane (R = 2), from 11 on one.
 template <int MODE>
 void launch_orth_mode(const mispec_ctx& ctx, const OrthArgs& a, int grid)
 {
-    // One instantiation per slot count (columns per wave, ceil(ncol / 4)): a wave then issues exactly the
-    // loads it needs — with a coarser set of sizes the surplus slots re-read column 0 and spend L1/L2 bandwidth.
-    const int slots = (a.ncol + 3) / 4;
+    const int slots = std::max((a.ncol + 3) / 4, 1);
     const bool two = slots <= 10;
     const dim3 g(static_cast<unsigned>(grid)), b(kThreads);
-    switch (slots)
-    {
-#define MISPEC_ORTH_CASE(S)                                                      \
-    case S:                                                                      \
-        if (two)                                                                 \
-            hipLaunchKernelGGL((k_orth<MODE, S, 2>), g, b, 0, ctx.stream, a);    \
-        else                                                                     \
-            hipLaunchKernelGGL((k_orth<MODE, S, 1>), g, b, 0, ctx.stream, a);    \
-        break;
-        case 0:
-            MISPEC_ORTH_CASE(1)
-            MISPEC_ORTH_CASE(2)
-            MISPEC_ORTH_CASE(3)
-            MISPEC_ORTH_CASE(4)
-            MISPEC_ORTH_CASE(5)
-            MISPEC_ORTH_CASE(6)
-            MISPEC_ORTH_CASE(7)
-            MISPEC_ORTH_CASE(8)
-            MISPEC_ORTH_CASE(9)
-            MISPEC_ORTH_CASE(10)
-            MISPEC_ORTH_CASE(11)
-            MISPEC_ORTH_CASE(12)
-            MISPEC_ORTH_CASE(13)
-            MISPEC_ORTH_CASE(14)
-            MISPEC_ORTH_CASE(15)
-        default:
-            hipLaunchKernelGGL((k_orth<MODE, 16, 1>), g, b, 0, ctx.stream, a);
-            break;
-#undef MISPEC_ORTH_CASE
-    }
+    const bool below16 = dispatch_slots<1, 15>(slots, [&](auto slots_c) {
+        constexpr int S = decltype(slots_c)::value;
+        if (two)
+            hipLaunchKernelGGL((k_orth<MODE, S, 2>), g, b, 0, ctx.stream, a);
+        else
+            hipLaunchKernelGGL((k_orth<MODE, S, 1>), g, b, 0, ctx.stream, a);
+    });
+    if (!below16)
+        hipLaunchKernelGGL((k_orth<MODE, 16, 1>), g, b, 0, ctx.stream, a);
+}
+
+// NW wavefronts of MAXS = ceil(ncol / NW) slots (16 and more: 16), R row pairs per lane and tile
+template <int MAXS, int R, int NW>
+void launch_orth_lagged_inst(const mispec_ctx& ctx, const OrthArgs& a, int grid)
+{
+    const dim3 g(static_cast<unsigned>(grid)), b(64 * NW);
+    if (a.onered)
+        hipLaunchKernelGGL((k_orth_lagged<MAXS, R, NW, true>), g, b, 0, ctx.stream, a);
+    else
+        hipLaunchKernelGGL((k_orth_lagged<MAXS, R, NW>), g, b, 0, ctx.stream, a);
 }
 
 void launch_orth_lagged(const mispec_ctx& ctx, const OrthArgs& a, int grid)
 {
-    const dim3 g(static_cast<unsigned>(grid));
     if (a.ncol >= kPanelCols)  // 64..127 finished columns: eight wavefronts of 16 columns
     {
-        const dim3 b8(512);
-        switch ((a.ncol + 7) / 8)
-        {
-#define MISPEC_LAG_CASE8(S)                                                     \
-    case S:                                                                     \
-        if (a.onered)                                                           \
-            hipLaunchKernelGGL((k_orth_lagged<S, 1, 8, true>), g, b8, 0, ctx.stream, a); \
-        else                                                                    \
-            hipLaunchKernelGGL((k_orth_lagged<S, 1, 8>), g, b8, 0, ctx.stream, a); \
-        break;
-            MISPEC_LAG_CASE8(8)
-            MISPEC_LAG_CASE8(9)
-            MISPEC_LAG_CASE8(10)
-            MISPEC_LAG_CASE8(11)
-            MISPEC_LAG_CASE8(12)
-            MISPEC_LAG_CASE8(13)
-            MISPEC_LAG_CASE8(14)
-            MISPEC_LAG_CASE8(15)
-            default:
-                if (a.onered)
-                    hipLaunchKernelGGL((k_orth_lagged<16, 1, 8, true>), g, b8, 0, ctx.stream, a);
-                else
-                    hipLaunchKernelGGL((k_orth_lagged<16, 1, 8>), g, b8, 0, ctx.stream, a);
-                break;
-#undef MISPEC_LAG_CASE8
-        }
+        if (!dispatch_slots<8, 15>((a.ncol + 7) / 8, [&](auto slots_c) { launch_orth_lagged_inst<decltype(slots_c)::value, 1, 8>(ctx, a, grid); }))
+            launch_orth_lagged_inst<16, 1, 8>(ctx, a, grid);
         return;
     }
-    const int slots = (a.ncol + 3) / 4;
+    const int slots = std::max((a.ncol + 3) / 4, 1);
     const bool two = slots <= 10;
-    const dim3 b(kThreads);
-    switch (slots)
-    {
-#define MISPEC_LAG_CASE(S)                                                  \
-    case S:                                                                 \
-        if (a.onered && two)                                                \
-            hipLaunchKernelGGL((k_orth_lagged<S, 2, 4, true>), g, b, 0, ctx.stream, a); \
-        else if (a.onered)                                                  \
-            hipLaunchKernelGGL((k_orth_lagged<S, 1, 4, true>), g, b, 0, ctx.stream, a); \
-        else if (two)                                                       \
-            hipLaunchKernelGGL((k_orth_lagged<S, 2, 4>), g, b, 0, ctx.stream, a); \
-        else                                                                \
-            hipLaunchKernelGGL((k_orth_lagged<S, 1, 4>), g, b, 0, ctx.stream, a); \
-        break;
-        case 0:
-            MISPEC_LAG_CASE(1)
-            MISPEC_LAG_CASE(2)
-            MISPEC_LAG_CASE(3)
-            MISPEC_LAG_CASE(4)
-            MISPEC_LAG_CASE(5)
-            MISPEC_LAG_CASE(6)
-            MISPEC_LAG_CASE(7)
-            MISPEC_LAG_CASE(8)
-            MISPEC_LAG_CASE(9)
-            MISPEC_LAG_CASE(10)
-            MISPEC_LAG_CASE(11)
-            MISPEC_LAG_CASE(12)
-            MISPEC_LAG_CASE(13)
-            MISPEC_LAG_CASE(14)
-            MISPEC_LAG_CASE(15)
-        default:
-            if (a.onered)
-                hipLaunchKernelGGL((k_orth_lagged<16, 1, 4, true>), g, b, 0, ctx.stream, a);
-            else
-                hipLaunchKernelGGL((k_orth_lagged<16, 1, 4>), g, b, 0, ctx.stream, a);
-            break;
-#undef MISPEC_LAG_CASE
-    }
+    const bool below16 = dispatch_slots<1, 15>(slots, [&](auto slots_c) {
+        constexpr int S = decltype(slots_c)::value;
+        if (two)
+            launch_orth_lagged_inst<S, 2, 4>(ctx, a, grid);
+        else
+            launch_orth_lagged_inst<S, 1, 4>(ctx, a, grid);
+    });
+    if (!below16)
+        launch_orth_lagged_inst<16, 1, 4>(ctx, a, grid);
 }
 
 }  // namespace

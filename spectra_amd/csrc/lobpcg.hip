@@ -12,6 +12,7 @@
 
 #include "csr.hpp"
 #include "csr_diag.hpp"
+#include "device_helpers.hpp"
 #include "krylov.hpp"
 #include "lobpcg_flow.hpp"
 
@@ -234,9 +235,7 @@ __global__ __launch_bounds__(kThreads) void k_lobpcg_resid(const double* __restr
     for (int j = 0; j < kLobpcgMaxBlock; j++)
         if (j < m)
         {
-            double v = acc[j];
-            for (int off = 32; off > 0; off >>= 1)
-                v += __shfl_down(v, off, 64);
+            const double v = wave_reduce_sum(acc[j]);
             if (lane == 0)
                 wsum[wave][j] = v;
         }

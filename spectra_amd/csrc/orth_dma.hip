@@ -1,30 +1,16 @@
 // The one-sweep orthogonalisation pass (krylov.hip k_orth_lagged, ORTH_LAGGED) with the basis streamed through an LDS ring by
-// LDS-DMA (`global_load_lds_dwordx4`) instead of through registers — round 6, VERDICT r05 item 2.
-//
-// Why: the register version issues a tile's 20 x 16-byte loads per lane, waits for all of them, computes, and only then issues
-// the next tile's loads; its SQ / TCC counters (profiles/r11a_pmc_sq_tcc_tcp_onesweep_c2_round5_tree.txt) show 90 128-byte requests in flight
-// per CU on average at 1214 cycles per request — the memory system is asked for 5.8 TB/s, not saturated.  Holding a second
-// tile in flight costs 80 more VGPRs per lane in registers and nothing in LDS: here every wavefront keeps DEPTH - 1 tiles of its
-// own columns in flight (wave-private regions of a DEPTH-slot ring, 1 KiB per column and tile = one DMA instruction), waits
-// with a COUNTED `s_waitcnt vmcnt(N)` — never 0 inside the loop —, and the per-tile barrier of the row-sum exchange is a bare
-// `s_barrier` that does not drain VMEM.  One 256-thread workgroup per CU (the ring is 3 x 44 KiB at 40 columns), grid-stride
-// over 128-row tiles; 256 partial records instead of 1024, so the record reduction behind the pass reads a quarter.
-//
-// Ordering rules used (MI355X_MICROARCH.md "Two waves per SIMD" item 7, cdna_hip_programming.md 5.7):
-//   * LDS-DMA data is ordered for a ds_read only by the ISSUING wave's covering vmcnt; other waves read it after a barrier the
-//     issuer reached behind that wait: a wave reads its own columns after its own wait, and f, u = src and column i-1
-//     (regions of waves 0, 1 and (i-1) % 4) after the exchange barrier of the tile;
-//   * the asm DMA is invisible to hipcc's waitcnt bookkeeping: every wait for it is an explicit statement; the loop holds no
-//     compiler-visible VMEM load, and wave 0's two stores per tile only make the counted wait conservative (vmcnt counts them
-//     too; loads complete in order among themselves, so "at most NL outstanding" still means tile t has landed);
-//   * a ring slot is refilled only behind the barrier that follows the last cross-wave read of it (slot of tile t-1 behind the
-//     barrier of tile t; every wave's LDS reads are retired by the lgkmcnt(0) in front of that barrier).
+// LDS-DMA (`global_load_lds_dwordx4`) instead of through registers — round 6, VERDICT r05 item 2.  Why, and the ordering rules the
+// loop below follows: orth_ring.hpp.  Here a wave reads its own columns after its own wait, and f, u = src and column i-1
+// (regions of waves 0, 1 and (i-1) % 4) after the exchange barrier of the tile.
 //
 // Arithmetic, record layout and the device-side step decisions are those of k_orth_lagged (same expressions per element; the
 // partial sums are grouped by 256 workgroups x 128-row tiles instead of 1024 x 256, so the reduced sums differ from the
 // register kernel's by rounding — as they do between any two grid sizes of that kernel).
 // Replaces Lanczos.h:171 of step i-1 + :106, :139, :145-152 of step i, as k_orth_lagged does.
+#include "device_helpers.hpp"
 #include "krylov.hpp"
+#include "orth_ring.hpp"
+#include "orth_step.hpp"
 
 using namespace mispec;
 
@@ -34,38 +20,6 @@ constexpr int kThreads = 256;
 constexpr int kNW = 4;
 constexpr int kRows = 128;  // rows of a tile: one 16-byte DMA element per lane and column covers two rows
 typedef __attribute__((address_space(3))) char lds_char;
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-
-// one wave-wide LDS-DMA: lane l's 16 bytes at gsrc land at LDS byte lds_dst + 16 l (lds_dst wave-uniform)
-template <bool NT>
-__device__ __forceinline__ void dma16(const double* gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    if (NT)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(gsrc), "s"(lds_dst)
-                     : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(gsrc), "s"(lds_dst)
-                     : "memory");
-}
 
 template <int MAXS, int DEPTH, bool ONERED>
 __global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a)
@@ -77,6 +31,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a)
     double* ring = reinterpret_cast<double*>(smem);            // [DEPTH][kNW][NL][128]
     double* psum = ring + DEPTH * kSlotDoubles;                 // [2][kNW][128]
     double* cs = psum + 2 * kNW * kRows;                        // [64]
+    static_assert((DEPTH * kSlotDoubles + 2 * kNW * kRows + 64) * sizeof(double) == ring_lds_bytes<MAXS, DEPTH>(), "carve-up and launcher disagree");
 
     if (a.status && *a.status != kStepOk)
         return;
@@ -216,55 +171,17 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_lagged_dma(OrthArgs a)
         slot = (DEPTH == 3) ? (slot == 2 ? 0 : slot + 1) : (slot ^ 1);
     }
 
-    double* rec = a.partials + blockIdx.x;
-#pragma unroll
-    for (int jj = 0; jj < MAXS; jj++)
-    {
-        const double s = wave_sum(acc[jj]);
-        const double c = wave_sum(chk[jj]);
-        const int j = w + kNW * jj;
-        if (lane == 0 && j < a.ncol)
-        {
-            rec[int64_t(j) * a.pstride] = s;
-            rec[int64_t(a.ncol + 1 + j) * a.pstride] = c;
-        }
-    }
-    if (w == 0)
-    {
-        b2 = wave_sum(b2);
-        dvi = wave_sum(dvi);
-        mx = wave_max(mx);
-        if (lane == 0)
-        {
-            rec[int64_t(a.ncol) * a.pstride] = dvi;
-            rec[kSlotBeta2 * a.pstride] = b2;
-            rec[kSlotMaxAbs * a.pstride] = mx;
-        }
-    }
-}
-
-template <int MAXS, int DEPTH, bool ONERED>
-void launch_inst(const mispec_ctx& ctx, const OrthArgs& a, int grid)
-{
-    const size_t lds = (size_t(DEPTH) * kNW * (MAXS + 1) * kRows + 2 * kNW * kRows + 64) * sizeof(double);
-    // (the attribute is per device and function; one context per device and process in practice, and setting it again is harmless)
-    static thread_local int attr_dev = -1;
-    if (attr_dev != ctx.device)
-    {
-        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_orth_lagged_dma<MAXS, DEPTH, ONERED>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        attr_dev = ctx.device;
-    }
-    hipLaunchKernelGGL((k_orth_lagged_dma<MAXS, DEPTH, ONERED>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx.stream, a);
+    lagged_record<kNW>(a, 0, a.ncol, w, lane, acc, chk, b2, dvi, mx);
 }
 
 template <int MAXS, int DEPTH>
 void launch_one(const mispec_ctx& ctx, const OrthArgs& a, int grid)
 {
+    const dim3 g(static_cast<unsigned>(grid)), b(kThreads);
     if (a.onered)
-        launch_inst<MAXS, DEPTH, true>(ctx, a, grid);
+        launch_with_dynamic_lds<k_orth_lagged_dma<MAXS, DEPTH, true>>(ctx, g, b, ring_lds_bytes<MAXS, DEPTH>(), a);
     else
-        launch_inst<MAXS, DEPTH, false>(ctx, a, grid);
+        launch_with_dynamic_lds<k_orth_lagged_dma<MAXS, DEPTH, false>>(ctx, g, b, ring_lds_bytes<MAXS, DEPTH>(), a);
 }
 
 }  // namespace
@@ -285,40 +202,16 @@ int launch_orth_lagged_dma(const mispec_ctx& ctx, const OrthArgs& a, int depth_o
     MISPEC_REQUIRE(a.pstride >= grid, "one-sweep orth kernel (LDS-DMA): partial-record stride smaller than the grid");
     const int slots = (a.ncol + 3) / 4;
     const bool three = slots <= 11 && depth_override != 2;
-    switch (slots)
-    {
-#define MISPEC_DMA_CASE(S)                \
-    case S:                               \
-        if (three)                        \
-            launch_one<S, 3>(ctx, a, grid); \
-        else                              \
-            launch_one<S, 2>(ctx, a, grid); \
-        break;
-        MISPEC_DMA_CASE(1)
-        MISPEC_DMA_CASE(2)
-        MISPEC_DMA_CASE(3)
-        MISPEC_DMA_CASE(4)
-        MISPEC_DMA_CASE(5)
-        MISPEC_DMA_CASE(6)
-        MISPEC_DMA_CASE(7)
-        MISPEC_DMA_CASE(8)
-        MISPEC_DMA_CASE(9)
-        MISPEC_DMA_CASE(10)
-        MISPEC_DMA_CASE(11)
-#undef MISPEC_DMA_CASE
-#define MISPEC_DMA_CASE2(S)             \
-    case S:                             \
-        launch_one<S, 2>(ctx, a, grid); \
-        break;
-        MISPEC_DMA_CASE2(12)
-        MISPEC_DMA_CASE2(13)
-        MISPEC_DMA_CASE2(14)
-        MISPEC_DMA_CASE2(15)
-        MISPEC_DMA_CASE2(16)
-#undef MISPEC_DMA_CASE2
-        default:
-            throw Error(MISPEC_EINVAL, "one-sweep orth kernel (LDS-DMA): needs 1 <= columns <= 63");
-    }
+    const bool ok = dispatch_slots<1, 11>(slots, [&](auto slots_c) {
+                        constexpr int S = decltype(slots_c)::value;
+                        if (three)
+                            launch_one<S, 3>(ctx, a, grid);
+                        else
+                            launch_one<S, 2>(ctx, a, grid);
+                    }) ||
+                    dispatch_slots<12, 16>(slots, [&](auto slots_c) { launch_one<decltype(slots_c)::value, 2>(ctx, a, grid); });
+    if (!ok)
+        throw Error(MISPEC_EINVAL, "one-sweep orth kernel (LDS-DMA): needs 1 <= columns <= 63");
     MISPEC_HIP(hipGetLastError());
     return grid;
 }

@@ -1,7 +1,7 @@
 // The passes over the basis of the REFERENCE control flow (Lanczos.h:145-152, :171-179) and of the Arnoldi process (Arnoldi.h:
 // 251-255) — k_orth's modes ORTH_VTF, ORTH_RESID_VTF, ORTH_CORRECT_VTF, ORTH_CORRECT_ONLY (krylov.hip) — with the basis streamed
 // through an LDS ring by LDS-DMA, as orth_dma.hip does for the one-sweep pass (round 6; the design, the ordering rules and the
-// counter evidence are in that file's header: one 256-thread workgroup per CU, every wavefront keeps DEPTH - 1 tiles of its own
+// counter evidence are in orth_ring.hpp: one 256-thread workgroup per CU, every wavefront keeps DEPTH - 1 tiles of its own
 // columns in flight, counted s_waitcnt vmcnt(N), a bare s_barrier per tile, a ring slot refilled only behind the barrier that
 // follows its last reader).  One column panel (<= 64 columns), vectors of at least 1024 tiles of 128 rows; everything else
 // keeps k_orth.  Same expressions per element and the same record layout as k_orth; the partial sums are grouped by 256
@@ -9,7 +9,9 @@
 //   VTF          c = V'x (+ |x|^2, max |x|)                       extra DMA column: x
 //   RESID_VTF    f = w - alpha v_i -> dst ; c = V'f ; norms       extra DMA columns: w (wave 0), v_i (wave 1)
 //   CORRECT_*    dst = src - V c_in ; norms ; (_VTF) c = V'dst    extra DMA column: src
+#include "device_helpers.hpp"
 #include "krylov.hpp"
+#include "orth_ring.hpp"
 
 using namespace mispec;
 
@@ -19,38 +21,6 @@ constexpr int kThreads = 256;
 constexpr int kNW = 4;
 constexpr int kRows = 128;
 typedef __attribute__((address_space(3))) char lds_char;
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-
-// one wave-wide LDS-DMA: lane l's 16 bytes at gsrc land at LDS byte lds_dst + 16 l (lds_dst wave-uniform)
-template <bool NT>
-__device__ __forceinline__ void dma16(const double* gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    if (NT)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(gsrc), "s"(lds_dst)
-                     : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(gsrc), "s"(lds_dst)
-                     : "memory");
-}
 
 template <int MODE, int MAXS, int DEPTH>
 __global__ __launch_bounds__(kThreads, 1) void k_orth_dma(OrthArgs a)
@@ -64,6 +34,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_dma(OrthArgs a)
     double* ring = reinterpret_cast<double*>(smem);  // [DEPTH][kNW][NL][128]
     double* psum = ring + DEPTH * kSlotDoubles;      // [2][kNW][128]
     double* cs = psum + 2 * kNW * kRows;             // [64]
+    static_assert((DEPTH * kSlotDoubles + 2 * kNW * kRows + 64) * sizeof(double) == ring_lds_bytes<MAXS, DEPTH>(), "carve-up and launcher disagree");
 
     if (a.status && *a.status != kStepOk)
         return;
@@ -198,7 +169,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_dma(OrthArgs a)
 #pragma unroll
         for (int jj = 0; jj < MAXS; jj++)
         {
-            const double s = wave_sum(acc[jj]);
+            const double s = wave_reduce_sum(acc[jj]);
             const int j = w + kNW * jj;
             if (lane == 0 && j < a.ncol)
                 rec[int64_t(a.col0 + j) * a.pstride] = s;
@@ -206,8 +177,8 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_dma(OrthArgs a)
     }
     if (w == 0 && a.norms)
     {
-        b2 = wave_sum(b2);
-        mx = wave_max(mx);
+        b2 = wave_reduce_sum(b2);
+        mx = wave_reduce_max(mx);
         if (lane == 0)
         {
             rec[kSlotBeta2 * a.pstride] = b2;
@@ -216,53 +187,17 @@ __global__ __launch_bounds__(kThreads, 1) void k_orth_dma(OrthArgs a)
     }
 }
 
-template <int MODE, int MAXS, int DEPTH>
-void launch_inst(const mispec_ctx& ctx, const OrthArgs& a, int grid)
-{
-    const size_t lds = (size_t(DEPTH) * kNW * (MAXS + 1) * kRows + 2 * kNW * kRows + 64) * sizeof(double);
-    static thread_local int attr_dev = -1;
-    if (attr_dev != ctx.device)
-    {
-        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_orth_dma<MODE, MAXS, DEPTH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        attr_dev = ctx.device;
-    }
-    hipLaunchKernelGGL((k_orth_dma<MODE, MAXS, DEPTH>), dim3(unsigned(grid)), dim3(kThreads), lds, ctx.stream, a);
-}
-
-// slots (columns per wavefront) in steps of two: half the instantiations; an odd count reads at most four surplus columns
+// slots (columns per wavefront) in steps of two: half the instantiations; an odd count reads at most four surplus columns.
+// Three ring slots up to 10 columns per wavefront, two from 12 on.
 template <int MODE>
 void launch_mode(const mispec_ctx& ctx, const OrthArgs& a, int grid)
 {
     const int slots = (a.ncol + 3) / 4;
-    switch ((slots + 1) / 2)
-    {
-        case 0:
-        case 1:
-            launch_inst<MODE, 2, 3>(ctx, a, grid);
-            break;
-        case 2:
-            launch_inst<MODE, 4, 3>(ctx, a, grid);
-            break;
-        case 3:
-            launch_inst<MODE, 6, 3>(ctx, a, grid);
-            break;
-        case 4:
-            launch_inst<MODE, 8, 3>(ctx, a, grid);
-            break;
-        case 5:
-            launch_inst<MODE, 10, 3>(ctx, a, grid);
-            break;
-        case 6:
-            launch_inst<MODE, 12, 2>(ctx, a, grid);
-            break;
-        case 7:
-            launch_inst<MODE, 14, 2>(ctx, a, grid);
-            break;
-        default:
-            launch_inst<MODE, 16, 2>(ctx, a, grid);
-            break;
-    }
+    // (the clamp to [1, 8] makes the dispatch total: its result needs no check)
+    dispatch_slots<1, 8>(std::min(std::max((slots + 1) / 2, 1), 8), [&](auto half_c) {
+        constexpr int S = 2 * decltype(half_c)::value, DEPTH = S <= 10 ? 3 : 2;
+        launch_with_dynamic_lds<k_orth_dma<MODE, S, DEPTH>>(ctx, dim3(unsigned(grid)), dim3(kThreads), ring_lds_bytes<S, DEPTH>(), a);
+    });
 }
 
 }  // namespace

@@ -13,40 +13,18 @@
 // columns are read (i_last: width of the last panel) where the reference flow reads about (3 - 1/npan) i.
 // Tiling, load pattern and the fixed-order cross-wave sums are k_orth's (krylov.hip): 256 threads, 128-row tiles, lane l owns
 // rows (2l, 2l+1), wavefront w owns the panel's columns w, w + 4, ...; no floating-point atomics.
+#include "device_helpers.hpp"
 #include "krylov.hpp"
+#include "orth_launch.hpp"
+#include "orth_step.hpp"
 
 using namespace mispec;
 
 namespace {
 
-typedef double v2d __attribute__((ext_vector_type(2)));
-
 constexpr int kThreads = 256;
 constexpr int kTileRows = 128;
 constexpr int kNW = 4;
-
-__device__ __forceinline__ double2 load_streamed(const double* p)  // non-temporal: the basis is streamed once per pass (k_orth)
-{
-    const v2d t = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p));
-    double2 r;
-    r.x = t.x;
-    r.y = t.y;
-    return r;
-}
-__device__ __forceinline__ double wave_reduce_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_reduce_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
 
 // The last panel of a panelled one-sweep step: columns [a.col0, a.col0 + a.ncol), a.ncol in 1..64, step i = a.col0 + a.ncol.
 // The running vector f - sum of the earlier panels is in column i (a.vout) when a correction is pending, else it is f itself.
@@ -170,31 +148,7 @@ __global__ __launch_bounds__(kThreads) void k_lagged_last_panel(OrthArgs a)
         }
     }
 
-    double* rec = a.partials + blockIdx.x;
-#pragma unroll
-    for (int jj = 0; jj < MAXS; jj++)
-    {
-        const double s = wave_reduce_sum(acc[jj]);
-        const double c = wave_reduce_sum(chk[jj]);
-        const int j = w + kNW * jj;
-        if (lane == 0 && j < a.ncol)
-        {
-            rec[int64_t(a.col0 + j) * a.pstride] = s;
-            rec[int64_t(step + 1 + a.col0 + j) * a.pstride] = c;
-        }
-    }
-    if (w == 0)
-    {
-        b2 = wave_reduce_sum(b2);
-        dvi = wave_reduce_sum(dvi);
-        mx = wave_reduce_max(mx);
-        if (lane == 0)
-        {
-            rec[int64_t(step) * a.pstride] = dvi;
-            rec[kSlotBeta2 * a.pstride] = b2;
-            rec[kSlotMaxAbs * a.pstride] = mx;
-        }
-    }
+    lagged_record<kNW>(a, a.col0, step, w, lane, acc, chk, b2, dvi, mx);
 }
 
 // A full panel (kPanelCols columns from a.col0) against the finished step `step`: c_j = <V_j, f> (a.dst) and chk_j = <V_j, v_i>
@@ -270,35 +224,15 @@ void launch_orth_lagged_wide(const mispec_ctx& ctx, const OrthArgs& a, int grid)
     OrthArgs last = a;
     last.col0 = (npan - 1) * kPanelCols;
     last.ncol = step - last.col0;
-    switch ((last.ncol + kNW - 1) / kNW)
-    {
-#define MISPEC_LAST_CASE(S)                                                               \
-    case S:                                                                               \
-        if (a.onered)                                                                     \
-            hipLaunchKernelGGL((k_lagged_last_panel<S, true>), g, b, 0, ctx.stream, last); \
-        else                                                                              \
-            hipLaunchKernelGGL((k_lagged_last_panel<S, false>), g, b, 0, ctx.stream, last); \
-        break;
-        MISPEC_LAST_CASE(1)
-        MISPEC_LAST_CASE(2)
-        MISPEC_LAST_CASE(3)
-        MISPEC_LAST_CASE(4)
-        MISPEC_LAST_CASE(5)
-        MISPEC_LAST_CASE(6)
-        MISPEC_LAST_CASE(7)
-        MISPEC_LAST_CASE(8)
-        MISPEC_LAST_CASE(9)
-        MISPEC_LAST_CASE(10)
-        MISPEC_LAST_CASE(11)
-        MISPEC_LAST_CASE(12)
-        MISPEC_LAST_CASE(13)
-        MISPEC_LAST_CASE(14)
-        MISPEC_LAST_CASE(15)
-        MISPEC_LAST_CASE(16)
-#undef MISPEC_LAST_CASE
-        default:
-            throw Error(MISPEC_EINVAL, "panelled one-sweep step: last panel wider than 64 columns");
-    }
+    const bool ok = dispatch_slots<1, 16>((last.ncol + kNW - 1) / kNW, [&](auto slots_c) {
+        constexpr int S = decltype(slots_c)::value;
+        if (a.onered)
+            hipLaunchKernelGGL((k_lagged_last_panel<S, true>), g, b, 0, ctx.stream, last);
+        else
+            hipLaunchKernelGGL((k_lagged_last_panel<S, false>), g, b, 0, ctx.stream, last);
+    });
+    if (!ok)
+        throw Error(MISPEC_EINVAL, "panelled one-sweep step: last panel wider than 64 columns");
     MISPEC_HIP(hipGetLastError());
     for (int q = 0; q + 1 < npan; q++)
     {

@@ -12,6 +12,7 @@
 #include <limits>
 #include <memory>
 
+#include "device_helpers.hpp"
 #include "krylov.hpp"
 
 using namespace mispec;
@@ -22,9 +23,7 @@ constexpr int kThreads = 256;
 
 __device__ __forceinline__ double block_sum(double v, double* red)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
+    v = wave_reduce_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0)
         red[threadIdx.x >> 6] = v;
@@ -167,9 +166,7 @@ __global__ __launch_bounds__(kThreads) void k_dot_record(const double* __restric
         mx = fmax(mx, fabs(xi));
     }
     s = block_sum(s, red);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        mx = fmax(mx, __shfl_down(mx, off, 64));
+    mx = wave_reduce_max(mx);
     __syncthreads();
     if ((threadIdx.x & 63) == 0)
         red[threadIdx.x >> 6] = mx;

@@ -11,6 +11,7 @@
 #include "staged.hpp"
 
 #include "csr.hpp"
+#include "device_helpers.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -18,16 +19,6 @@
 namespace mispec {
 
 namespace {
-
-typedef double v2d __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double st_wave_sum(double v)  // the reduction tree of the CSR kernels' records
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
 
 __device__ __forceinline__ void st_store(v2d p, double* at)  // streamed: read back by phase 2 only after 1.2 GB more (plain stores
 {                                                             // measured the same, profiles/r07g)
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(kStRowThreads) void k_staged_rows(const int32_t* __
         }
         if (EPI)
         {
-            const double t = st_wave_sum(contrib);
+            const double t = wave_reduce_sum(contrib);  // the reduction tree of the CSR kernels' records
             if (lane == 0)
                 red[j * kWavesPer + w] = t;
         }

@@ -258,13 +258,6 @@ void tiles_spmv_host(const HostTiles& T, int64_t nrows, const double* x, double*
 }
 
 namespace {
-__device__ __forceinline__ double tile_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_down(v, off, 64);
-    return v;
-}
 // product rounded on its own (no FMA with the accumulation): the sums are those of the CSR kernels, bit for bit
 __device__ __forceinline__ double rounded_product(double a, double b)
 {
@@ -384,7 +377,7 @@ __global__ __launch_bounds__(kTileThreads) void k_spmv_tiles(const int64_t* __re
         if (EPI)
         {
             // cross-wave sum through the accumulator slots of this block, which every thread has read by now
-            const double t = tile_wave_sum(contrib);
+            const double t = wave_reduce_sum(contrib);
             __syncthreads();
             double* red = acc + j * 256;
             if ((tid & 63) == 0 && tid < 256)

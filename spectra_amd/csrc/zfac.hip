@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "device_helpers.hpp"
 #include "zcsr.hpp"
 #include "zfac_flow.hpp"
 
@@ -38,22 +39,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kVqBatch = 8;    // k_zvq: tile loads in flight per thread
 
 inline int64_t chunks_for(int64_t n) { return (n + kChunk - 1) / kChunk; }
-
-// sum over the 64 lanes of a wave in a fixed order; lane 0 holds the result
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ inline double wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fmax(v, __shfl_down(v, o, 64));
-    return v;
-}
 
 // stage 1 of out[j] = X[:, j]^H y: block (chunk b, column group g) writes part[j * nchunks + b] for its kColGroup columns
 __global__ __launch_bounds__(kThreads) void k_zdotc_partial(int64_t n, const double2* __restrict__ X, int64_t ldx, int ncols,
@@ -84,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_zdotc_partial(int64_t n, const dou
 #pragma unroll
     for (int c = 0; c < kColGroup; c++)
     {
-        const double a = wave_sum(re[c]), b = wave_sum(im[c]);
+        const double a = wave_reduce_sum(re[c]), b = wave_reduce_sum(im[c]);
         if (lane == 0)
         {
             red[wave][2 * c] = a;
@@ -113,8 +98,8 @@ __global__ __launch_bounds__(kThreads) void k_zdotc_final(const double2* __restr
         re += p[b].x;
         im += p[b].y;
     }
-    re = wave_sum(re);
-    im = wave_sum(im);
+    re = wave_reduce_sum(re);
+    im = wave_reduce_sum(im);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0)
     {
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void k_zabsmax_partial(int64_t n, const d
     double m = 0.0;
     for (int64_t i = r0 + threadIdx.x; i < r1; i += kThreads)
         m = fmax(m, hypot(x[i].x, x[i].y));
-    m = wave_max(m);
+    m = wave_reduce_max(m);
     if ((threadIdx.x & 63) == 0)
         red[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -216,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void k_zabsmax_final(const double* __rest
     double m = 0.0;
     for (int64_t b = threadIdx.x; b < nchunks; b += kThreads)
         m = fmax(m, part[b]);
-    m = wave_max(m);
+    m = wave_reduce_max(m);
     if ((threadIdx.x & 63) == 0)
         red[threadIdx.x >> 6] = m;
     __syncthreads();

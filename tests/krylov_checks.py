@@ -1,5 +1,6 @@
 """Checks of the REAL orthogonalisation and V*Q kernels (spectra_amd/csrc/krylov.hip: k_orth, k_reduce_partials, k_scale,
-k_lanczos_epilogue, k_vq, k_axpby; csrc/orth_dma_modes.hip: k_orth_dma; the step code of csrc/fac.hip) one step at a time, written
+k_lanczos_epilogue, k_vq, k_axpby; csrc/orth_dma_modes.hip: k_orth_dma; their launchers' slot dispatch: csrc/orth_launch.hpp; the
+step code of csrc/fac.hip) one step at a time, written
 against the Factorization interface (init, factorize_from, matrix_V / matrix_H, vector_f, f_norm, num_operations, ritz_vectors,
 compress_V): tests/test_gpu_krylov_kernels.py runs them on sa.Factorization, tests/test_host_krylov_checks.py on a float64 numpy
 stand-in of the reference's control flow, honest and with targeted defects.

@@ -1,7 +1,7 @@
 """The real orthogonalisation and V*Q kernels one step at a time (tests/krylov_checks.py: scripted operators, long-double
 references, bounds counted from the kernels' source), at the smallest shapes at which each branch of csrc/krylov.hip,
-csrc/orth_dma_modes.hip and the step code of csrc/fac.hip exists.  The sizes that depend on the device are derived from its CU
-count; the figures in the comments are for 256 CUs.  tests/test_host_krylov_checks.py shows, without a GPU, that an honest
+csrc/orth_dma_modes.hip (launchers: csrc/orth_launch.hpp) and the step code of csrc/fac.hip exists.  The sizes that depend on
+the device are derived from its CU count; the figures in the comments are for 256 CUs.  tests/test_host_krylov_checks.py shows, without a GPU, that an honest
 float64 implementation meets these bounds and that each targeted defect exceeds them at least 100 times."""
 import numpy as np
 import pytest
