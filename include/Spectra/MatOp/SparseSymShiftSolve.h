@@ -90,6 +90,13 @@ public:
         internal::check(mispec_symshift_solve_host(m_solver.get(), x_in, y_out));
     }
 
+    // Y[:, c] = inv(A - sigma I) * X[:, c] for c < k: column-major host blocks with ldx, ldy >= rows().  One block solve on the
+    // device (panels of columns share a pass over the factor); every column has the bits of perform_op on it alone.
+    void perform_op_block(const Scalar* X, Index ldx, Index k, Scalar* Y, Index ldy) const
+    {
+        internal::check(mispec_symshift_solve_block_host(m_solver.get(), X, ldx, static_cast<int>(k), Y, ldy));
+    }
+
     mispec_ctx* mispec_context() const { return m_ctx.get(); }
     const mispec_symshift* mispec_solver() const { return m_solver.get(); }
 };

@@ -97,6 +97,12 @@ public:
     // y_out = inv(A - sigma * B) * x_in, host pointers
     void perform_op(const Scalar* x_in, Scalar* y_out) const { internal::check(mispec_symshift_solve_host(m_solver.get(), x_in, y_out)); }
 
+    // Y[:, c] = inv(A - sigma B) * X[:, c] for c < k: column-major host blocks with ldx, ldy >= rows(); the bits of perform_op
+    void perform_op_block(const Scalar* X, Index ldx, Index k, Scalar* Y, Index ldy) const
+    {
+        internal::check(mispec_symshift_solve_block_host(m_solver.get(), X, ldx, static_cast<int>(k), Y, ldy));
+    }
+
     mispec_ctx* mispec_context() const { return m_ctx.get(); }
     const mispec_symshift* mispec_solver() const { return m_solver.get(); }
 };

@@ -26,11 +26,14 @@
 #define MISPEC_SPECTRA_LOBPCG_SOLVER_H
 
 #include "../../mispec_extras.h"  // outside the hot path: declared apart from the thin shim
+#include "../../mispec_lobpcg_pre.h"  // the solver preconditioner (ties the solver to the shift-and-invert operator)
 #include <memory>
 #include <stdexcept>
 #include <type_traits>
 
 #include "../MatOp/SparseSymMatProd.h"
+#include "../MatOp/SparseSymShiftSolve.h"
+#include "../MatOp/SymShiftInvert.h"
 #include "../Util/SelectionRule.h"
 #include "../internal/Dense.h"
 #include "../internal/Device.h"
@@ -52,6 +55,18 @@ private:
     std::shared_ptr<Operator> m_B, m_T;
     const Index m_n, m_nev;
     std::shared_ptr<mispec_lobpcg> m_solver;
+    std::shared_ptr<const void> m_F;  // a shared copy of the solver given as the preconditioner
+
+    template <typename Solver>
+    void set_solver(const Solver& F)
+    {
+        if (F.rows() != m_n || F.cols() != m_n)
+            throw std::invalid_argument("Wrong size");
+        auto keep = std::make_shared<Solver>(F);
+        internal::check(mispec_lobpcg_set_preconditioner_solver(m_solver.get(), keep->mispec_solver()));
+        m_F = keep;
+        m_T.reset();
+    }
 
     void bind(const Matrix& X)
     {
@@ -109,6 +124,18 @@ public:
     void setPreconditioner(const SparseArg& T)
     {
         setPreconditioner(Operator(T));
+    }
+    // R <- (K - sigma M)^{-1} R with the factorisation held by a shift-and-invert operator of a matrix near A (set_shift() before
+    // compute(); positive definite), applied as one block solve per iteration.  A shared copy keeps the solver alive.
+    template <int Uplo, int Flags, typename StorageIndex>
+    void setPreconditioner(const SparseSymShiftSolve<Scalar, Uplo, Flags, StorageIndex>& F)
+    {
+        set_solver(F);
+    }
+    template <int UploA, int UploB, int FlagsA, int FlagsB, typename IndexA, typename IndexB>
+    void setPreconditioner(const SymShiftInvert<Scalar, Sparse, Sparse, UploA, UploB, FlagsA, FlagsB, IndexA, IndexB>& F)
+    {
+        set_solver(F);
     }
     // R <- diag(A)^-1 R, fused into the residual kernel; needs a positive diagonal
     void setJacobiPreconditioner() { internal::check(mispec_lobpcg_set_jacobi(m_solver.get(), 1)); }

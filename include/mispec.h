@@ -73,6 +73,9 @@ const char* mispec_version(void);
  *                                                                        k <= 131072, all: any k, 0: store every diagonal; same bits)
  *   host_threads    integer >= 1                                         upper bound on the host threads of the ingest / the shift solve's
  *                                                                        host-side factorisation (tests: results do not depend on it)
+ *   shift_block     auto (default) | 0 | 2 | 4                           block shift solve (mispec_symshift_solve_block): the widest panel of
+ *                                                                        columns that shares one pass over the factor (0: one solve per
+ *                                                                        column; same bits)
  *   shift           comma list of lds=0|1, batch=8|16|32, lanes=8|16|32|64, block_inverse=<MiB>, factor=host|device, wave=0|1,
  *                   profile=0|1, each key at most once — banded shift solve: kernel variants that must agree (tests), set_shift's
  *                   phases on stderr
@@ -377,6 +380,24 @@ int mispec_symshift_solve(const mispec_symshift* S, const double* x_dev, double*
 int mispec_symshift_refinement_info(const mispec_symshift* S, int* refine_steps, int64_t* boosted_pivots,
                                     double* min_pivot_ratio, double* probe_backward_error);
 int mispec_symshift_solve_host(const mispec_symshift* S, const double* x_host, double* y_host); /* literal perform_op */
+/* Y[:, c] = (A - sigma B)^{-1} X[:, c], c < k, with DEVICE pointers, enqueued on the context's stream.  X and Y are column-major
+ * n x k blocks with ldx, ldy >= n and must not overlap.  The columns are cut into panels of 4, then 2 columns (option shift_block:
+ * 2 | 4 cap the width, 0 allows none), each of which reads the factor once where a panel kernel exists: the narrow-band
+ * partitioned levels (half-bandwidth <= 8: sweeps, explicit chunk inverses, separator right-hand sides, back substitution) and the
+ * dense inverses (n <= 4096, last level).  Wide levels (half-bandwidth 9 ... 64) and remaining single columns run the single
+ * kernels per column.  Every column has exactly the bits mispec_symshift_solve gives for it alone, on every path (pencils,
+ * reordered matrices, general operators, indefinite shifts with their refinement steps).
+ * MISPEC_EINVAL: NULL pointer, k < 1, ldx < n or ldy < n; MISPEC_ELOGIC: set_shift has not been called. */
+int mispec_symshift_solve_block(const mispec_symshift* S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);
+/* The same on host pointers, staged through device blocks kept on the handle. */
+int mispec_symshift_solve_block_host(const mispec_symshift* S, const double* X_host, int64_t ldx, int k, double* Y_host, int64_t ldy);
+/* The cut of k >= 1 columns into panels, host only (no device needed): widths[0 .. *count) in the order the block solve runs them,
+ * each 4, 2 or 1 (a single column), non-increasing, summing to k.  panel: 0 = what option shift_block says, 1 = single columns
+ * only, 2 | 4 = the widest panel.  MISPEC_EINVAL for k < 1, another panel, a NULL pointer or max_widths < *count. */
+int mispec_symshift_block_plan(int k, int panel, int* widths, int max_widths, int* count);
+/* Duration (ms, HIP events on the context stream) of `reps` back-to-back block solves after one that is not timed. */
+int mispec_symshift_solve_block_time(const mispec_symshift* S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy,
+                                     int reps, float* ms_per_call);
 
 /* ---------------------------------------------------------------------------
  * Factorisation A V = V H + f e' kept in HBM — replaces LinAlg/Arnoldi.h + LinAlg/Lanczos.h.

@@ -20,7 +20,7 @@ from ._capi import MispecError, Profile, build_library, check, lib
 __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatProd", "SparseSymShiftSolve", "SymEigsSolver",
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
-           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "dia_sym_plan", "mirror_triangle_device",
+           "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "shift_block_plan", "dia_sym_plan", "mirror_triangle_device",
            "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
@@ -246,6 +246,33 @@ def spmm_plan(k, panel=0):
     count = C.c_int(0)
     check(lib().mispec_spmm_plan(int(k), int(panel), out, cap, C.byref(count)))
     return [out[i] for i in range(count.value)]
+
+
+def shift_block_plan(k, panel=0):
+    """The panel widths a block shift solve of k columns runs, in order (mispec_symshift_block_plan; host only): each 4, 2 or 1.
+    panel: 0 what option `shift_block` says, 1 single columns only, 2 | 4 the widest panel."""
+    cap = max(int(k), 1)
+    out = (C.c_int * cap)()
+    count = C.c_int(0)
+    check(lib().mispec_symshift_block_plan(int(k), int(panel), out, cap, C.byref(count)))
+    return [out[i] for i in range(count.value)]
+
+
+class _ShiftBlock:
+    """Block solves of the shift-and-invert operators (mispec_symshift_solve_block): k right-hand sides, panels of 4 and 2 columns
+    per pass over the factor, every column with the bits of perform_op on it alone."""
+
+    def perform_op_block(self, X_in):
+        X = np.asfortranarray(X_in, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError("perform_op_block: X must be an n x k array")
+        Y = np.empty(X.shape, order="F")
+        check(lib().mispec_symshift_solve_block_host(self.h, _dp(X), max(self.n, 1), X.shape[1], _dp(Y), max(self.n, 1)))
+        return Y
+
+    def solve_block_device(self, x_ptr, ldx, k, y_ptr, ldy):
+        """Y[:, :k] = (A - sigma B)^{-1} X[:, :k] on device pointers (column-major, ldx, ldy >= n), enqueued on the context's stream."""
+        check(lib().mispec_symshift_solve_block(self.h, C.c_void_p(int(x_ptr)), int(ldx), int(k), C.c_void_p(int(y_ptr)), int(ldy)))
 
 
 def dia_sym_plan(offsets, reach=-1):
@@ -615,7 +642,7 @@ def _synth(cls, n, offsets, seed, symmetric, ctx):
     return obj
 
 
-class SparseSymShiftSolve:
+class SparseSymShiftSolve(_ShiftBlock):
     """MatOp/SparseSymShiftSolve.h: y = (A - sigma I)^{-1} x, solved on the GPU after set_shift(sigma)."""
 
     def __init__(self, mat, uplo="L", ctx=None):
@@ -851,7 +878,7 @@ class SparseCholesky:
             pass
 
 
-class SymShiftInvert:
+class SymShiftInvert(_ShiftBlock):
     """MatOp/SymShiftInvert.h (sparse A, sparse B): y = (A - sigma B)^{-1} x, factored on the GPU at set_shift(sigma)."""
 
     def __init__(self, A, B, uplo_a="L", uplo_b="L", ctx=None):
@@ -1267,7 +1294,8 @@ class LOBPCGInfo(enum.IntEnum):
 class LOBPCGSolver:
     """contrib/LOBPCGSolver.h on the device: the m smallest (or largest) eigenpairs of A x = lambda B x by LOBPCG.
     op, B: SparseSymMatProd (unsharded); X0: dense n x m start block, or nev columns of SimpleRandom streams (seed j + 1);
-    preconditioner: a sparse device operator (SparseSymMatProd, or SparseGenMatProd) applied as R <- T R, or "jacobi" (1 / diag A); constraints: dense n x c block the
+    preconditioner: a sparse device operator (SparseSymMatProd, or SparseGenMatProd) applied as R <- T R, a positive definite
+    SparseSymShiftSolve / SymShiftInvert whose block solve is applied (a reference is kept), or "jacobi" (1 / diag A); constraints: dense n x c block the
     eigenvectors are kept B-orthogonal to.  1 <= m <= 21, m < n, c <= 21, m + c < n."""
 
     def __init__(self, op, X0=None, nev=None, B=None, preconditioner=None, constraints=None):
@@ -1294,6 +1322,10 @@ class LOBPCGSolver:
             if preconditioner != "jacobi":
                 raise ValueError("LOBPCGSolver: the preconditioner is a SparseSymMatProd or the string 'jacobi'")
             check(lib().mispec_lobpcg_set_jacobi(self.h, 1))
+        elif isinstance(preconditioner, _ShiftBlock):
+            # a factorisation (SparseSymShiftSolve, SymShiftInvert) applied as R <- (K - sigma M)^{-1} R, one block solve per iteration
+            self.T = preconditioner
+            check(lib().mispec_lobpcg_set_preconditioner_solver(self.h, preconditioner.h))
         elif preconditioner is not None:
             if not isinstance(preconditioner, _DeviceMatrix):
                 raise TypeError("LOBPCGSolver: the preconditioner is a SparseSymMatProd or the string 'jacobi'")
@@ -1497,7 +1529,7 @@ class SymEigsShiftSolver(SymEigsSolver):
             raise TypeError("SymEigsShiftSolver: pass a SparseSymShiftSolve operator")
 
 
-class SparseGenRealShiftSolve:
+class SparseGenRealShiftSolve(_ShiftBlock):
     """MatOp/SparseGenRealShiftSolve.h: y = (A - sigma I)^{-1} x for a general sparse A (dense device factorisation,
     n <= 4096)."""
 

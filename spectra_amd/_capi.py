@@ -127,6 +127,10 @@ SIGNATURES = {
     "mispec_symshift_solve": (C.c_int, [_vp, _vp, _vp]),
     "mispec_symshift_refinement_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64), _dp, _dp]),
     "mispec_symshift_solve_host": (C.c_int, [_vp, _dp, _dp]),
+    "mispec_symshift_solve_block": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64]),
+    "mispec_symshift_solve_block_host": (C.c_int, [_vp, _dp, C.c_int64, C.c_int, _dp, C.c_int64]),
+    "mispec_symshift_block_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "mispec_symshift_solve_block_time": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, C.POINTER(C.c_float)]),
     "mispec_fac_create": (C.c_int, [_vp, _vp, op_fn, _vp, C.c_int64, C.c_int, C.c_int, _vpp]),
     "mispec_fac_create_shiftsolve": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vpp]),
     "mispec_fac_create_device_op": (C.c_int, [_vp, device_op_fn, _vp, C.c_int64, C.c_int, C.c_int, _vpp]),
@@ -327,6 +331,12 @@ SIGNATURES = {
     "mispec_hess_eigen_host": (C.c_int, [C.c_int, _dp, _dp, _dp]),
 }
 
+# include/mispec_lobpcg_pre.h: what ties the LOBPCG solver of the extras library to the shift-and-invert operator (the entry
+# points of mispec.h / mispec_extras.h above are the complete list of those two headers)
+LOBPCG_PRE_SIGNATURES = {
+    "mispec_lobpcg_set_preconditioner_solver": (C.c_int, [_vp, _vp]),
+}
+
 _lib = None
 
 
@@ -340,7 +350,7 @@ def lib():
                 "(hipcc --offload-arch=gfx950).  This package has no CPU fallback.")
         L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
         X = None
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(LOBPCG_PRE_SIGNATURES.items()):
             if name.startswith(EXTRAS_PREFIXES):
                 # components outside the hot path: their own library on top of this one (resolved through the handle of the
                 # first, so that Python code keeps saying lib().mispec_davidson_create)

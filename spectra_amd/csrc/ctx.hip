@@ -79,6 +79,8 @@ constexpr OptionEntry kOptions[] = {
     {Opt::host_threads, "host_threads", "MISPEC_HOST_THREADS", Kind::integer, {}, 1, kMaxInt,
      "upper bound on the host threads of the ingest and of the shift solve's host-side factorisation"},
     {Opt::shift, "shift", "MISPEC_SHIFT", Kind::shift, {}, 0, 0, "kernel variants of the banded shift solve"},
+    {Opt::shift_block, "shift_block", "MISPEC_SHIFT_BLOCK", Kind::choice, {"auto", "0", "2", "4"}, 0, 0,
+     "widest panel of a block shift solve (0: one solve per column)"},
 };
 static_assert(sizeof(kOptions) / sizeof(kOptions[0]) == size_t(Opt::count), "one entry per option");
 constexpr bool entries_in_order()

@@ -92,6 +92,90 @@ __global__ __launch_bounds__(64) void k_row_gemv_serial(int64_t rows, int64_t co
     y[r] = acc;
 }
 
+// k_row_gemv for a panel of K vectors: the row is read once and applied to every column.  Per column the operations of k_row_gemv
+// in its order, written out (the single kernel leaves them to the compiler's contraction; its ISA has, per 16-byte piece,
+// t = m.y * v.y rounded, t = fma(m.x, v.x, t), acc += t, an fma for the odd last column, and an fma per entry without VEC).
+template <bool VEC, int K>
+__global__ __launch_bounds__(kGemvThreads) void k_row_gemv_panel(int64_t rows, int64_t cols, int64_t ld, const double* __restrict__ M,
+                                                                  const double* __restrict__ X, int64_t ldx, double* __restrict__ Y,
+                                                                  int64_t ldy)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t r = int64_t(blockIdx.x) * (kGemvThreads / 64) + (threadIdx.x >> 6);
+    if (r >= rows)
+        return;
+    const double* a = M + r * ld;
+    double acc[K][4];
+#pragma unroll
+    for (int c = 0; c < K; c++)
+        acc[c][0] = acc[c][1] = acc[c][2] = acc[c][3] = 0.0;
+    const auto piece = [](double s, const double2 m, const double2 v) { return __dadd_rn(s, fma(m.x, v.x, __dmul_rn(m.y, v.y))); };
+    if (VEC)
+    {
+        const double2* a2 = reinterpret_cast<const double2*>(a);
+        const int64_t pairs = cols >> 1;
+        int64_t p = lane;
+        for (; p + 192 < pairs; p += 256)
+        {
+            const double2 m0 = a2[p], m1 = a2[p + 64], m2 = a2[p + 128], m3 = a2[p + 192];
+#pragma unroll
+            for (int c = 0; c < K; c++)
+            {
+                const double2* x2 = reinterpret_cast<const double2*>(X + int64_t(c) * ldx);
+                const double2 v0 = x2[p], v1 = x2[p + 64], v2 = x2[p + 128], v3 = x2[p + 192];
+                acc[c][0] = piece(acc[c][0], m0, v0);
+                acc[c][1] = piece(acc[c][1], m1, v1);
+                acc[c][2] = piece(acc[c][2], m2, v2);
+                acc[c][3] = piece(acc[c][3], m3, v3);
+            }
+        }
+        for (; p < pairs; p += 64)
+        {
+            const double2 m0 = a2[p];
+#pragma unroll
+            for (int c = 0; c < K; c++)
+                acc[c][0] = piece(acc[c][0], m0, reinterpret_cast<const double2*>(X + int64_t(c) * ldx)[p]);
+        }
+        if ((cols & 1) && lane == 0)
+        {
+#pragma unroll
+            for (int c = 0; c < K; c++)
+                acc[c][1] = fma(a[cols - 1], X[int64_t(c) * ldx + cols - 1], acc[c][1]);
+        }
+    }
+    else
+    {
+        int64_t j = lane;
+        for (; j + 192 < cols; j += 256)
+        {
+            const double m0 = a[j], m1 = a[j + 64], m2 = a[j + 128], m3 = a[j + 192];
+#pragma unroll
+            for (int c = 0; c < K; c++)
+            {
+                const double* x = X + int64_t(c) * ldx;
+                acc[c][0] = fma(m0, x[j], acc[c][0]);
+                acc[c][1] = fma(m1, x[j + 64], acc[c][1]);
+                acc[c][2] = fma(m2, x[j + 128], acc[c][2]);
+                acc[c][3] = fma(m3, x[j + 192], acc[c][3]);
+            }
+        }
+        for (; j < cols; j += 64)
+        {
+            const double m0 = a[j];
+#pragma unroll
+            for (int c = 0; c < K; c++)
+                acc[c][0] = fma(m0, X[int64_t(c) * ldx + j], acc[c][0]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < K; c++)
+    {
+        const double s = wave_reduce_sum(__dadd_rn(__dadd_rn(acc[c][0], acc[c][1]), __dadd_rn(acc[c][2], acc[c][3])));
+        if (lane == 0)
+            Y[int64_t(c) * ldy + r] = s;
+    }
+}
+
 void ensure_stage(const mispec_dense& D)
 {
     if (D.stage_x.n < size_t(D.cols) + 2)
@@ -121,6 +205,34 @@ void launch_row_gemv(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t
         hipLaunchKernelGGL(k_row_gemv<true>, grid, block, 0, ctx.stream, rows, cols, ld, M, x, y);
     else
         hipLaunchKernelGGL(k_row_gemv<false>, grid, block, 0, ctx.stream, rows, cols, ld, M, x, y);
+    MISPEC_HIP(hipGetLastError());
+}
+
+void launch_row_gemv_panel(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t rows, int64_t cols, const double* X, int64_t ldx,
+                           int k, double* Y, int64_t ldy, bool storage_order_if_small)
+{
+    if (rows <= 0 || k <= 0)
+        return;
+    // the single product picks its kernel per vector from the vector's alignment: a panel kernel runs only where every column
+    // makes the same choice (an odd ldx makes every second column 8-byte aligned only), and never for the storage-order kernel
+    const auto vec_of = [&](int c) {
+        return (ld % 2 == 0) && (reinterpret_cast<uintptr_t>(X + int64_t(c) * ldx) % 16 == 0) && (reinterpret_cast<uintptr_t>(M) % 16 == 0);
+    };
+    bool same = true;
+    for (int c = 1; c < k; c++)
+        same = same && vec_of(c) == vec_of(0);
+    if ((k != 2 && k != 4) || !same || (storage_order_if_small && rows * cols <= kSerialGemvEntries))
+    {
+        for (int c = 0; c < k; c++)
+            launch_row_gemv(ctx, M, ld, rows, cols, X + int64_t(c) * ldx, Y + int64_t(c) * ldy, storage_order_if_small);
+        return;
+    }
+    const dim3 grid(unsigned((rows + kGemvThreads / 64 - 1) / (kGemvThreads / 64))), block(kGemvThreads);
+    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, ctx.stream, rows, cols, ld, M, X, ldx, Y, ldy); };
+    if (vec_of(0))
+        k == 4 ? launch(&k_row_gemv_panel<true, 4>) : launch(&k_row_gemv_panel<true, 2>);
+    else
+        k == 4 ? launch(&k_row_gemv_panel<false, 4>) : launch(&k_row_gemv_panel<false, 2>);
     MISPEC_HIP(hipGetLastError());
 }
 

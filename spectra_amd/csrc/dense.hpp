@@ -20,4 +20,9 @@ namespace mispec {
 // order like a CPU row-dot and the sparse kernels (the dense product operators ask for it; see k_row_gemv_serial)
 void launch_row_gemv(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t rows, int64_t cols, const double* x, double* y,
                      bool storage_order_if_small = false);
+// Y[:, c] = M X[:, c] for c < k (column-major blocks): with k = 2 or 4 the matrix is read once for the panel, every column summed
+// in launch_row_gemv's order — the bits of k single products.  Any other k, columns of mixed 16-byte alignment and the
+// storage-order case are k single products.
+void launch_row_gemv_panel(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t rows, int64_t cols, const double* X, int64_t ldx,
+                           int k, double* Y, int64_t ldy, bool storage_order_if_small = false);
 }  // namespace mispec

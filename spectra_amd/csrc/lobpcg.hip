@@ -1,5 +1,5 @@
 // LOBPCG on the device (replaces contrib/LOBPCGSolver.h of the reference): the HIP backend of lobpcg_flow.hpp, its three block
-// kernels and the C ABI (include/mispec_extras.h, mispec_lobpcg_*).
+// kernels and the C ABI (include/mispec_extras.h, mispec_lobpcg_*; include/mispec_lobpcg_pre.h for the solver preconditioner).
 //
 // What stays in HBM: S = [X | R | P], its images AS and BS (two buffers each, n x 3m), the constraints Y and BY, 1 / diag(A).  What the
 // host does: see lobpcg_flow.hpp.  Products with A, B and the sparse preconditioner are block products (launch_spmm); the combinations
@@ -15,6 +15,8 @@
 #include "device_helpers.hpp"
 #include "krylov.hpp"
 #include "lobpcg_flow.hpp"
+#include "shiftsolve.hpp"
+#include "../../include/mispec_lobpcg_pre.h"
 
 using namespace mispec;
 
@@ -478,6 +480,7 @@ struct HipBackend
     const mispec_csr* A = nullptr;
     const mispec_csr* B = nullptr;
     const mispec_csr* T = nullptr;
+    const mispec_symshift* F = nullptr;  // preconditioner given as a shift solve (replaces T)
     int64_t n = 0, ldv = 0;
     LobpcgWork work;
     DevBuf<double> dinv;
@@ -505,7 +508,13 @@ struct HipBackend
     void random_col(double* col, uint64_t seed) { launch_simple_random(*ctx, col, 0, n, seed); }
     void apply_A(const double* X, int k, double* Y) { launch_spmm(*A, X, ldv, k, Y, ldv); }
     void apply_B(const double* X, int k, double* Y) { launch_spmm(*B, X, ldv, k, Y, ldv); }
-    void apply_T(const double* X, int k, double* Y) { launch_spmm(*T, X, ldv, k, Y, ldv); }
+    void apply_T(const double* X, int k, double* Y)
+    {
+        if (F)
+            launch_shiftsolve_block(*F, X, ldv, k, Y, ldv);  // the factorisation of a nearby matrix, one pass over it per panel
+        else
+            launch_spmm(*T, X, ldv, k, Y, ldv);
+    }
     void gram(const double* U, int p, const double* W, int q, bool symmetric, double* G) { work.gram(U, ldv, p, W, ldv, q, n, symmetric, G); }
     void vq(const double* V, int mm, const double* Q_host, int ldq, int p, double* X)
     {
@@ -600,7 +609,28 @@ extern "C" int mispec_lobpcg_set_preconditioner(mispec_lobpcg* S, const mispec_c
             require_operator(S, T, "LOBPCGSolver: the preconditioner must be an unsharded matrix of A's shape and context");
         S->ctx->make_current();
         S->be.T = T;
+        S->be.F = nullptr;
         S->flow->set_T(T != nullptr);
+    });
+}
+
+// T = (K - sigma M)^{-1} as a factorisation held by F: applied to the active columns by launch_shiftsolve_block.  T has to be positive
+// definite; a banded factorisation knows the signs of its pivots, on the dense path (n <= 4096) definiteness is the caller's duty.
+extern "C" int mispec_lobpcg_set_preconditioner_solver(mispec_lobpcg* S, const mispec_symshift* F)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(S, "mispec_lobpcg_set_preconditioner_solver: NULL argument");
+        if (F)
+        {
+            MISPEC_REQUIRE(F->ctx == S->ctx && F->n == S->be.n, "LOBPCGSolver: the preconditioner must be a solver of A's size and context");
+            MISPEC_REQUIRE(!F->general, "LOBPCGSolver: the preconditioner must be a symmetric solver");
+            MISPEC_REQUIRE(!F->factored || F->dense || F->negative_pivots == 0,
+                           "LOBPCGSolver: the preconditioner must be positive definite (the factorisation met negative pivots)");
+        }
+        S->ctx->make_current();
+        S->be.T = nullptr;
+        S->be.F = F;
+        S->flow->set_T(F != nullptr);
     });
 }
 
@@ -639,6 +669,8 @@ extern "C" int mispec_lobpcg_set_jacobi(mispec_lobpcg* S, int on)
             MISPEC_HIP(hipStreamSynchronize(st));
             S->be.dinv.swap(inv);
         }
+        if (on)
+            S->be.F = nullptr;  // Jacobi replaces a solver preconditioner (the flow drops T itself)
         S->flow->set_jacobi(on != 0);
     });
 }
@@ -674,6 +706,14 @@ extern "C" int mispec_lobpcg_compute(mispec_lobpcg* S, int selection, int64_t ma
         // Util/SelectionRule.h: LargestAlge = 3, SmallestAlge = 7
         MISPEC_REQUIRE(selection == 3 || selection == 7, "LOBPCGSolver: the selection rule must be SmallestAlge or LargestAlge");
         MISPEC_REQUIRE(maxit >= 0 && tol_abs >= 0.0, "LOBPCGSolver: maxit and the tolerance cannot be negative");
+        if (S->be.F)
+        {
+            if (!S->be.F->factored)
+                throw Error(MISPEC_ELOGIC, "LOBPCGSolver: the preconditioner's set_shift() has not been called");
+            // the shift may have been set again since the solver was given
+            MISPEC_REQUIRE(S->be.F->dense || S->be.F->negative_pivots == 0,
+                           "LOBPCGSolver: the preconditioner must be positive definite (the factorisation met negative pivots)");
+        }
         S->ctx->make_current();
         *nconv = S->flow->compute(selection == 3, maxit, tol_abs);
     });

@@ -28,6 +28,8 @@
 //   * dense (n <= 4096, any sparsity — the reference's own test fixtures are of this kind): LU with partial
 //     pivoting of the dense A - sigma I on the host, explicit inverse, and a dense GEMV kernel per step.
 // Anything else (large n with large bandwidth) is rejected: a general sparse LU on the GPU is out of scope.
+// Block form (launch_shiftsolve_block): k right-hand sides in panels of 4 and 2 columns that read the factor once — panel kernels
+// for the narrow levels and the dense inverses, the single kernels per column elsewhere; every column has the bits of a single solve.
 #include "shiftsolve.hpp"
 #include "reorder.hpp"
 #include "dense.hpp"
@@ -816,6 +818,358 @@ __global__ __launch_bounds__(kBackThreads) void k_back_subst(int64_t N, int b, i
     }
 }
 
+// ---- panel forms: K right-hand sides per pass over the factor (launch_shiftsolve_block) ------------------------------------
+// Every kernel below reads what its single-vector counterpart reads ONCE and applies it to the K columns of a column-major panel
+// (column c of f at f + c * ldf, ...).  Per column the operations and their order are the counterpart's, written out with fma()
+// where the counterpart's ISA has v_fma_f64 (the compiler contracts every `acc += a * x` / `acc -= w * x` of k_block_gemv,
+// k_sep_rhs and k_back_subst; none keeps a rounded product): column c of the result has the bits of a single solve.
+
+// k_chunk_solve_lds for K columns: the further columns live in registers of the same lane (hist[K][B]) and in K LDS segments; a
+// batch of factor entries is loaded once and runs K independent fma chains, which also fills the issue slots that the one
+// dependent chain of the single kernel leaves empty.  Loop bounds stay wave-uniform and the scheduling barrier stays between a
+// batch's loads and its recurrences, for the reasons given above k_chunk_solve_lds.
+template <int B, int U, int K>
+__global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t N, int64_t L, ChunkStore cs, int ldl, int chunks_per_block,
+                                                                         const double* __restrict__ Lf, const double* __restrict__ Dinv,
+                                                                         const double* __restrict__ f, int64_t ldf, double* __restrict__ y,
+                                                                         int64_t ldy)
+{
+    extern __shared__ double seg[];  // K columns x chunks_per_block chunks x ldl
+    const int64_t P = cs.P;
+    const bool tail_block = blockIdx.x == gridDim.x - 1;  // the last chunk alone
+    const int64_t first = tail_block ? P - 1 : int64_t(blockIdx.x) * chunks_per_block;
+    const int nch = tail_block ? 1 : int(min(int64_t(chunks_per_block), P - 1 - first));
+    const int m = int(tail_block ? N - (P - 1) * L : L - B);
+    const int mr = (m + U - 1) / U * U;
+    const int lane = threadIdx.x, nl = blockDim.x;
+    const int cstride = chunks_per_block * ldl;  // doubles per column of the panel
+    for (int col = 0; col < K; col++)
+    {
+        double* const sc = seg + col * cstride;
+        const double* src = f + int64_t(col) * ldf + first * L;
+        const int64_t total = tail_block ? m : int64_t(nch) * L;
+        constexpr int kInFlight = 32;
+        int c = 0;
+        int64_t k = lane;
+        while (k >= L && !tail_block)
+        {
+            k -= L;
+            c++;
+        }
+        for (int64_t i0 = lane; i0 < total; i0 += int64_t(kInFlight) * nl)
+        {
+            double t[kInFlight];
+#pragma unroll
+            for (int q = 0; q < kInFlight; q++)
+                t[q] = (i0 + int64_t(q) * nl < total) ? src[i0 + int64_t(q) * nl] : 0.0;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < kInFlight; q++)
+            {
+                if (i0 + int64_t(q) * nl < total && k < m)
+                    sc[c * ldl + k] = t[q];
+                k += nl;
+                while (k >= L && !tail_block)
+                {
+                    k -= L;
+                    c++;
+                }
+            }
+        }
+        for (int kz = m + lane; kz < mr; kz += nl)
+            for (int cz = 0; cz < nch; cz++)
+                sc[cz * ldl + kz] = 0.0;
+    }
+    __syncthreads();
+    if (lane < nch)
+    {
+        const int64_t p = first + lane;
+        double* const zp = seg + lane * ldl;  // column c: zp + c * cstride
+        const double* const lfw = Lf + cs.lf(p, 0, 0);
+        const double* const dvw = Dinv + cs.dinv(p, 0);
+        double hist[K][B];
+        const auto forward = [&](const double (&lf)[U][B], int k0) {
+#pragma unroll
+            for (int u = 0; u < U; u++)
+            {
+#pragma unroll
+                for (int c = 0; c < K; c++)
+                {
+                    double acc = zp[c * cstride + k0 + u];
+#pragma unroll
+                    for (int d = B - 1; d >= 0; d--)
+                        acc = fma(-lf[u][d], hist[c][d], acc);
+#pragma unroll
+                    for (int d = B - 1; d > 0; d--)
+                        hist[c][d] = hist[c][d - 1];
+                    hist[c][0] = acc;
+                    zp[c * cstride + k0 + u] = acc;
+                }
+            }
+        };
+        const auto backward = [&](const double (&lf)[U][B], const double (&di)[U], int k0) {  // rows k0 + U - 1 down to k0
+#pragma unroll
+            for (int u = U - 1; u >= 0; u--)
+            {
+#pragma unroll
+                for (int c = 0; c < K; c++)
+                {
+                    double acc = __dmul_rn(zp[c * cstride + k0 + u], di[u]);
+#pragma unroll
+                    for (int d = B - 1; d >= 0; d--)
+                        acc = fma(-lf[u][d], hist[c][d], acc);
+#pragma unroll
+                    for (int d = B - 1; d > 0; d--)
+                        hist[c][d] = hist[c][d - 1];
+                    hist[c][0] = acc;
+                    zp[c * cstride + k0 + u] = acc;
+                }
+            }
+        };
+        const auto load_forward = [&](double (&lf)[U][B], int k0) {
+            const double* const lfk = lfw + int64_t(k0 >> 1) * (B * 128);
+#pragma unroll
+            for (int j = 0; j < U / 2; j++)
+#pragma unroll
+                for (int d = 0; d < B; d++)
+                {
+                    const double2 v = *reinterpret_cast<const double2*>(lfk + (j * B + d) * 128);
+                    lf[2 * j][d] = v.x;
+                    lf[2 * j + 1][d] = v.y;
+                }
+        };
+        const auto load_backward = [&](double (&lf)[U][B], double (&di)[U], int k0) {  // entry d of row k0 + u + d + 1
+            const double* const lfk = lfw + int64_t(k0 >> 1) * (B * 128);
+            const double* const dvk = dvw + int64_t(k0 >> 1) * 128;
+#pragma unroll
+            for (int j = U / 2 - 1; j >= 0; j--)
+            {
+                const double2 v = *reinterpret_cast<const double2*>(dvk + j * 128);
+                di[2 * j] = v.x;
+                di[2 * j + 1] = v.y;
+            }
+#pragma unroll
+            for (int d = 0; d < B; d++)
+#pragma unroll
+                for (int j = (U + d) / 2; j >= (d + 1) / 2; j--)
+                {
+                    const double2 v = *reinterpret_cast<const double2*>(lfk + (j * B + d) * 128);
+                    if (2 * j - d - 1 >= 0 && 2 * j - d - 1 < U)
+                        lf[2 * j - d - 1][d] = v.x;
+                    if (2 * j - d >= 0 && 2 * j - d < U)
+                        lf[2 * j - d][d] = v.y;
+                }
+        };
+#pragma unroll
+        for (int c = 0; c < K; c++)
+#pragma unroll
+            for (int d = 0; d < B; d++)
+                hist[c][d] = 0.0;
+        for (int k0 = 0; k0 < mr; k0 += U)
+        {
+            double lf[U][B];
+            load_forward(lf, k0);
+            __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first use
+            forward(lf, k0);
+        }
+#pragma unroll
+        for (int c = 0; c < K; c++)
+#pragma unroll
+            for (int d = 0; d < B; d++)
+                hist[c][d] = 0.0;
+        for (int k0 = mr - U; k0 >= 0; k0 -= U)
+        {
+            double di[U], lf[U][B];
+            load_backward(lf, di, k0);
+            __builtin_amdgcn_sched_barrier(0);
+            backward(lf, di, k0);
+        }
+    }
+    __syncthreads();
+    for (int col = 0; col < K; col++)
+    {
+        const double* const sc = seg + col * cstride;
+        double* dst = y + int64_t(col) * ldy + first * L;
+        for (int k = lane; k < m; k += nl)
+        {
+#pragma unroll 8
+            for (int c = 0; c < nch; c++)
+                dst[int64_t(c) * L + k] = sc[c * ldl + k];
+        }
+    }
+}
+
+// k_block_gemv for K columns: binv is read once per panel; per column the same partial sum per wavefront and the same combination
+template <int K>
+__global__ __launch_bounds__(64 * kBlockGemvWaves) void k_block_gemv_panel(int64_t N, int b, int64_t L, int64_t P, int64_t ld,
+                                                                            const double* __restrict__ inv, const double* __restrict__ f,
+                                                                            int64_t ldf, double* __restrict__ y, int64_t ldy)
+{
+    __shared__ double fs[K][256];
+    __shared__ double part[K][kBlockGemvWaves][64];
+    const int64_t p = blockIdx.y;
+    const int64_t row0 = p * L;
+    const int64_t m = ((p == P - 1) ? N : (row0 + L - b)) - row0;  // <= 256: wants_block_inverse
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t j = int64_t(blockIdx.x) * 64 + lane;
+    for (int64_t k = threadIdx.x; k < m; k += 64 * kBlockGemvWaves)
+#pragma unroll
+        for (int c = 0; c < K; c++)
+            fs[c][k] = f[int64_t(c) * ldf + row0 + k];
+    __syncthreads();
+    const double* blk = inv + size_t(p) * ld * ld;
+    double acc[K];
+#pragma unroll
+    for (int c = 0; c < K; c++)
+        acc[c] = 0.0;
+    if (j < m)
+    {
+        int64_t k = w;
+        for (; k + 3 * kBlockGemvWaves < m; k += 4 * kBlockGemvWaves)
+        {
+            const double a0 = blk[k * ld + j], a1 = blk[(k + kBlockGemvWaves) * ld + j], a2 = blk[(k + 2 * kBlockGemvWaves) * ld + j],
+                         a3 = blk[(k + 3 * kBlockGemvWaves) * ld + j];
+#pragma unroll
+            for (int c = 0; c < K; c++)
+            {
+                acc[c] = fma(a0, fs[c][k], acc[c]);
+                acc[c] = fma(a1, fs[c][k + kBlockGemvWaves], acc[c]);
+                acc[c] = fma(a2, fs[c][k + 2 * kBlockGemvWaves], acc[c]);
+                acc[c] = fma(a3, fs[c][k + 3 * kBlockGemvWaves], acc[c]);
+            }
+        }
+        for (; k < m; k += kBlockGemvWaves)
+        {
+            const double a0 = blk[k * ld + j];
+#pragma unroll
+            for (int c = 0; c < K; c++)
+                acc[c] = fma(a0, fs[c][k], acc[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < K; c++)
+        part[c][w][lane] = acc[c];
+    __syncthreads();
+    if (w == 0 && j < m)
+    {
+#pragma unroll
+        for (int c = 0; c < K; c++)
+        {
+            double s = part[c][0][lane];
+#pragma unroll
+            for (int q = 1; q < kBlockGemvWaves; q++)
+                s = __dadd_rn(s, part[c][q][lane]);
+            y[int64_t(c) * ldy + row0 + j] = s;
+        }
+    }
+}
+
+// k_sep_rhs for K columns: the band rows of a separator row are loaded once
+template <int B, int K>
+__global__ __launch_bounds__(kThreads) void k_sep_rhs_panel(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ band,
+                                                             const double* __restrict__ f, int64_t ldf, const double* __restrict__ y,
+                                                             int64_t ldy, double* __restrict__ g, int64_t ldg)
+{
+    const int64_t s = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+    if (s >= (P - 1) * b)
+        return;
+    const int64_t p = s / b;
+    const int64_t sep0 = (p + 1) * L - b, r = sep0 + (s % b);
+    double mu[B], ml[B];
+#pragma unroll
+    for (int d = 1; d <= B; d++)
+    {
+        const int64_t ju = r - d;
+        const bool up = d <= b && ju >= 0 && ju < sep0;
+        mu[d - 1] = up ? band[r * (b + 1) + d] : 0.0;
+        const int64_t jl = r + d;
+        const bool lo = d <= b && jl < N && jl >= sep0 + b;
+        ml[d - 1] = lo ? band[jl * (b + 1) + d] : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < K; c++)
+    {
+        const double* const yc = y + int64_t(c) * ldy;
+        double yu[B], yl[B];
+#pragma unroll
+        for (int d = 1; d <= B; d++)
+        {
+            const int64_t ju = r - d, jl = r + d;
+            yu[d - 1] = (d <= b && ju >= 0 && ju < sep0) ? yc[ju] : 0.0;
+            yl[d - 1] = (d <= b && jl < N && jl >= sep0 + b) ? yc[jl] : 0.0;
+        }
+        double acc = f[int64_t(c) * ldf + r];
+#pragma unroll
+        for (int d = 1; d <= B; d++)
+        {
+            if (d <= b && r - d >= 0 && r - d < sep0)
+                acc = fma(-mu[d - 1], yu[d - 1], acc);
+            if (d <= b && r + d < N && r + d >= sep0 + b)
+                acc = fma(-ml[d - 1], yl[d - 1], acc);
+        }
+        g[int64_t(c) * ldg + s] = acc;
+    }
+}
+
+// k_back_subst for K columns: W is read once per panel, the 2b separator unknowns of every column stay wave-uniform operands
+template <int K>
+__global__ __launch_bounds__(kBackThreads) void k_back_subst_panel(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ W,
+                                                                   const double* __restrict__ y, int64_t ldy, const double* __restrict__ xs,
+                                                                   int64_t ldxs, double* __restrict__ x, int64_t ldx)
+{
+    const int64_t p = blockIdx.x;
+    const int64_t row0 = p * L;
+    const int64_t end = (p == P - 1) ? N : row0 + L;
+    const int64_t sep0 = (p == P - 1) ? N : row0 + L - b;
+    const double* const xprev = xs + (p - 1) * b;  // p > 0
+    const double* const xnext = xs + p * b;        // p < P - 1
+    const int64_t piece0 = row0 + int64_t(blockIdx.y) * kBackPiece;
+    const int64_t piece1 = (piece0 + kBackPiece < end) ? piece0 + kBackPiece : end;
+    for (int64_t r = piece0 + threadIdx.x; r < piece1; r += kBackThreads)
+    {
+        if (r >= sep0)
+        {
+#pragma unroll
+            for (int c = 0; c < K; c++)
+                x[int64_t(c) * ldx + r] = xnext[int64_t(c) * ldxs + r - sep0];
+            continue;
+        }
+        double acc[K];
+#pragma unroll
+        for (int c = 0; c < K; c++)
+            acc[c] = y[int64_t(c) * ldy + r];
+        const auto side = [&](const double* Wc, const double* xv) {
+            int q = 0;
+            for (; q + 8 <= b; q += 8)
+            {
+                double w[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    w[i] = Wc[int64_t(q + i) * N];
+#pragma unroll
+                for (int c = 0; c < K; c++)
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+                        acc[c] = fma(-w[i], xv[int64_t(c) * ldxs + q + i], acc[c]);
+            }
+            for (; q < b; q++)
+            {
+                const double w = Wc[int64_t(q) * N];
+#pragma unroll
+                for (int c = 0; c < K; c++)
+                    acc[c] = fma(-w, xv[int64_t(c) * ldxs + q], acc[c]);
+            }
+        };
+        if (p > 0)
+            side(W + r, xprev);
+        if (p < P - 1)
+            side(W + int64_t(b) * N + r, xnext);
+#pragma unroll
+        for (int c = 0; c < K; c++)
+            x[int64_t(c) * ldx + r] = acc[c];
+    }
+}
+
 // dst = src with sigma subtracted from the diagonal entries (column 0 of the n x (b+1) row-major band)
 // (pencil: dst = src - sigma * srcB entry by entry, the bands share one layout)
 __global__ __launch_bounds__(kThreads) void k_band_shift(int64_t total, int bw, double sigma, const double* __restrict__ src,
@@ -1240,6 +1594,9 @@ struct mispec::BandLevel
     DevBuf<double> binv;  // partitioned level with few chunks: explicit inverses of the interiors, P blocks of binv_ld x binv_ld
     int64_t binv_ld = 0;
     DevBuf<double> linv, linvt;  // last level, Cholesky use only: C^{-1} and C^{-T} of the level's M = C C' (row-major)
+    // block solves: y, g, xs for the widest panel (column-major, leading dimensions pld / pld_s), allocated at the first one
+    mutable DevBuf<double> py, pg, pxs;
+    mutable int64_t pld = 0, pld_s = 0;
     std::unique_ptr<BandLevel> next;
 };
 
@@ -1881,6 +2238,120 @@ void solve_level(const mispec_ctx& ctx, const BandLevel& lev, const double* f, d
     MISPEC_HIP(hipGetLastError());
 }
 
+// ---- a level for a panel of K = 2 or 4 columns (launch_shiftsolve_block) ---------------------------------------------------------
+// Each step takes its panel kernel where there is one — the narrow levels (half-bandwidth <= 8, not cs.wide) and the dense last
+// level — and otherwise the single-vector kernel column by column on the same panel buffers, so a wide level in the middle of the
+// recursion (b = 8 has a Schur band of 15) loops while the levels around it run as panels.
+constexpr int kMaxPanel = 4;
+// Sweeps of a panel of 4 at half-bandwidths up to this run as two launches of the 2-column kernel (64 chunks per workgroup, batches of
+// 32 rows): the 4-column kernel there (32 chunks per workgroup, 200 registers parked in AGPRs) measured 0.0637 against 0.0607 ms per
+// column at n = 2e6, b = 3, while at b = 8 it is the faster one (0.130 against 0.160)
+constexpr int kSweepPairsUpTo = 4;
+
+void panel_scratch(const BandLevel& top)
+{
+    for (const BandLevel* l = &top; l && l->P > 1; l = l->next.get())
+        if (!l->py.p)
+        {
+            l->pld = round_up(l->N, 2);  // even: every column 16-byte aligned, like the single solve's own buffers
+            l->pld_s = round_up((l->P - 1) * l->b, 2);
+            l->py.alloc(size_t(l->pld) * kMaxPanel);
+            l->pg.alloc(size_t(l->pld_s) * kMaxPanel);
+            l->pxs.alloc(size_t(l->pld_s) * kMaxPanel);
+        }
+}
+
+// the interior sweeps of a narrow level for K columns; false: no panel kernel for this level under the options in force
+template <int K>
+bool launch_chunk_solve_panel(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, double* y, int64_t ldy)
+{
+    const ShiftOptions so = shift_options();
+    const int U = lev.b <= 4 ? 32 : 16;
+    if (lev.cs.wide || so.lds == 0 || lev.P <= 1 || lev.b < 1 || lev.b > 8 || (so.batch != 0 && so.batch != U))
+        return false;
+    // K columns of a 64-chunk workgroup do not fit the LDS of a CU (66 KB each): fewer chunks per workgroup for wider panels
+    int chunks = std::min(solve_lanes(lev.P), K == 4 ? 32 : 64);
+    const auto whole = [U](int64_t m) { return (m + U - 1) / U * U; };
+    const int64_t ldl = std::max<int64_t>(whole(lev.L - lev.b), (whole(lev.N - (lev.P - 1) * lev.L) + chunks - 1) / chunks) | 1;
+    const size_t lds_bytes = size_t(K) * size_t(chunks) * size_t(ldl) * sizeof(double);
+    if (lds_bytes > 160 * 1024)
+        return false;
+    const dim3 grid(unsigned((lev.P - 1 + chunks - 1) / chunks) + 1);  // + the last chunk's own workgroup
+    const auto launch = [&](auto kernel) {
+        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+        hipLaunchKernelGGL(kernel, grid, dim3(kStageThreads), lds_bytes, ctx.stream, lev.N, lev.L, lev.cs, int(ldl), chunks, lev.Lf.p,
+                           lev.Dinv.p, f, ldf, y, ldy);
+    };
+    switch (lev.b)
+    {
+        case 1: launch(&k_chunk_solve_lds_panel<1, 32, K>); break;
+        case 2: launch(&k_chunk_solve_lds_panel<2, 32, K>); break;
+        case 3: launch(&k_chunk_solve_lds_panel<3, 32, K>); break;
+        case 4: launch(&k_chunk_solve_lds_panel<4, 32, K>); break;
+        case 5: launch(&k_chunk_solve_lds_panel<5, 16, K>); break;
+        case 6: launch(&k_chunk_solve_lds_panel<6, 16, K>); break;
+        case 7: launch(&k_chunk_solve_lds_panel<7, 16, K>); break;
+        case 8: launch(&k_chunk_solve_lds_panel<8, 16, K>); break;
+    }
+    MISPEC_HIP(hipGetLastError());
+    return true;
+}
+
+template <int K>
+void solve_level_panel(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, double* x, int64_t ldx)
+{
+    if (lev.P == 1)
+    {
+        if (lev.inv.p)
+            launch_row_gemv_panel(ctx, lev.inv.p, lev.N, lev.N, lev.N, f, ldf, K, x, ldx);
+        else
+            for (int c = 0; c < K; c++)
+                launch_chunk_solve(ctx, lev, dim3(1), f + c * ldf, x + c * ldx);
+        return;
+    }
+    const bool narrow = !lev.cs.wide && lev.b <= 8;
+    double* const y = lev.py.p;
+    double* const g = lev.pg.p;
+    double* const xs = lev.pxs.p;
+    const int64_t ldy = lev.pld, lds = lev.pld_s;
+    if (lev.binv.p)
+    {
+        hipLaunchKernelGGL(k_block_gemv_panel<K>, dim3(unsigned((lev.binv_ld + 63) / 64), unsigned(lev.P)), dim3(64 * kBlockGemvWaves), 0,
+                           ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.binv_ld, lev.binv.p, f, ldf, y, ldy);
+        MISPEC_HIP(hipGetLastError());
+    }
+    else if (K == 4 && kSweepPairsUpTo >= lev.b && launch_chunk_solve_panel<2>(ctx, lev, f, ldf, y, ldy))
+        launch_chunk_solve_panel<2>(ctx, lev, f + 2 * ldf, ldf, y + 2 * ldy, ldy);
+    else if (!launch_chunk_solve_panel<K>(ctx, lev, f, ldf, y, ldy))
+        for (int c = 0; c < K; c++)
+            launch_chunk_solve(ctx, lev, dim3(unsigned((lev.P + kChunkThreads - 1) / kChunkThreads)), f + c * ldf, y + c * ldy);
+    if (narrow)
+    {
+        const dim3 grid(unsigned(((lev.P - 1) * lev.b + kThreads - 1) / kThreads));
+        if (lev.b <= 4)
+            hipLaunchKernelGGL((k_sep_rhs_panel<4, K>), grid, dim3(kThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, ldf, y, ldy,
+                               g, lds);
+        else
+            hipLaunchKernelGGL((k_sep_rhs_panel<8, K>), grid, dim3(kThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, ldf, y, ldy,
+                               g, lds);
+    }
+    else
+        for (int c = 0; c < K; c++)
+            launch_sep_rhs(ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f + c * ldf, y + c * ldy, g + c * lds);
+    MISPEC_HIP(hipGetLastError());
+    solve_level_panel<K>(ctx, *lev.next, g, lds, xs, lds);
+    const int64_t longest = std::max<int64_t>(lev.L, lev.N - (lev.P - 1) * lev.L);
+    const dim3 bgrid(unsigned(lev.P), unsigned((longest + kBackPiece - 1) / kBackPiece));
+    if (narrow)
+        hipLaunchKernelGGL(k_back_subst_panel<K>, bgrid, dim3(kBackThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, y, ldy, xs, lds, x,
+                           ldx);
+    else
+        for (int c = 0; c < K; c++)
+            hipLaunchKernelGGL(k_back_subst, bgrid, dim3(kBackThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, y + c * ldy, xs + c * lds,
+                               x + c * ldx);
+    MISPEC_HIP(hipGetLastError());
+}
+
 // ---- G^{-1} and G^{-T} for the factor G G' = M of a positive definite band (SparseCholesky beyond the dense limit) -------
 // In the nested order (chunk interiors, then separators, recursively) M = G G' with
 //   G = [ L_II D^{1/2}  0 ; M_SI L_II^{-T} D^{-1/2}  G_S ],   G_S G_S' = Schur complement of the separators,
@@ -2180,6 +2651,121 @@ void launch_shiftsolve(const mispec_symshift& S, const double* x_dev, double* y_
             refine_once(S, x, y);
         if (S.reordered())
             from_stored_order(S, S.perm_y.p, y_dev);
+    }
+}
+
+// ---- block solve: k right-hand sides, panels of 4 and 2 columns ------------------------------------------------------------
+namespace {
+// Panel widths that `auto` uses, widest first: a width stays here only while its panels measured faster than as many single
+// solves on the paths that have panel kernels (tools/bench_shift_block.py).
+constexpr int kAutoWidths[] = {4, 2};
+
+template <int K>
+void shiftsolve_panel(const mispec_symshift& S, const double* X, int64_t ldx, double* Y, int64_t ldy)
+{
+    if (S.dense)
+    {
+        launch_row_gemv_panel(*S.ctx, S.inverse.p, S.n, S.n, S.n, X, ldx, K, Y, ldy);
+        return;
+    }
+    const int64_t pld = S.panel_ld;
+    const double* x = X;
+    double* y = Y;
+    int64_t lx = ldx, ly = ldy;
+    if (S.reordered())  // gather and scatter per column, as the single solve does them
+    {
+        for (int c = 0; c < K; c++)
+            to_stored_order(S, X + c * ldx, S.panel_px.p + c * pld);
+        x = S.panel_px.p;
+        y = S.panel_py.p;
+        lx = ly = pld;
+    }
+    solve_level_panel<K>(*S.ctx, *S.top, x, lx, y, ly);
+    hipStream_t st = S.ctx->stream;
+    for (int it = 0; it < S.refine_steps; it++)  // refine_once for every column: the residual and the update are elementwise kernels
+    {
+        for (int c = 0; c < K; c++)
+            hipLaunchKernelGGL(k_band_resid, row_blocks(S.n), dim3(kThreads), 0, st, S.n, S.band_b, S.sigma, S.band0_dev.p,
+                               S.pencil ? S.bandB0_dev.p : nullptr, x + c * lx, y + c * ly, S.panel_r.p + c * pld);
+        MISPEC_HIP(hipGetLastError());
+        solve_level_panel<K>(*S.ctx, *S.top, S.panel_r.p, pld, S.panel_dy.p, pld);
+        for (int c = 0; c < K; c++)
+            hipLaunchKernelGGL(k_add_inplace, row_blocks(S.n), dim3(kThreads), 0, st, S.n, y + c * ly, S.panel_dy.p + c * pld);
+        MISPEC_HIP(hipGetLastError());
+    }
+    if (S.reordered())
+        for (int c = 0; c < K; c++)
+            from_stored_order(S, S.panel_py.p + c * pld, Y + c * ldy);
+}
+
+// the panel buffers of the handle and of the levels in place now, for the widest panel; nothing is allocated once they exist
+void block_scratch(const mispec_symshift& S)
+{
+    if (S.dense)
+        return;
+    S.panel_ld = round_up(S.n, 2);
+    const size_t need = size_t(S.panel_ld) * kMaxPanel;
+    if (S.refine_steps > 0 && S.panel_r.n < need)
+    {
+        S.panel_r.alloc(need);
+        S.panel_dy.alloc(need);
+    }
+    if (S.reordered() && S.panel_px.n < need)
+    {
+        S.panel_px.alloc(need);
+        S.panel_py.alloc(need);
+    }
+    panel_scratch(*S.top);
+}
+}  // namespace
+
+std::vector<int> shiftsolve_block_plan(int k, int panel)
+{
+    MISPEC_REQUIRE(k >= 1, "mispec_symshift_block_plan: k < 1");
+    MISPEC_REQUIRE(panel == 0 || panel == 1 || panel == 2 || panel == 4,
+                   "mispec_symshift_block_plan: panel is one of 0 (option shift_block), 1, 2, 4");
+    int allowed[2] = {0, 0}, na = 0;
+    const ShiftBlock opt = panel == 0 ? option_choice(Opt::shift_block, ShiftBlock::automatic) : ShiftBlock::automatic;
+    if (panel == 0 && opt == ShiftBlock::automatic)
+        for (const int w : kAutoWidths)
+            allowed[na++] = w;
+    else
+    {
+        const int cap = panel ? panel : (opt == ShiftBlock::off ? 1 : opt == ShiftBlock::w2 ? 2 : 4);
+        for (int w = 4; w >= 2; w >>= 1)
+            if (w <= cap)
+                allowed[na++] = w;
+    }
+    std::vector<int> widths;
+    for (int i = 0; i < na; i++)
+        for (; k >= allowed[i]; k -= allowed[i])
+            widths.push_back(allowed[i]);
+    widths.insert(widths.end(), size_t(k), 1);
+    return widths;
+}
+
+void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy)
+{
+    MISPEC_REQUIRE(X_dev && Y_dev, "mispec_symshift_solve_block: NULL argument");
+    MISPEC_REQUIRE(k >= 1, "mispec_symshift_solve_block: k < 1");
+    MISPEC_REQUIRE(ldx >= S.n && ldy >= S.n, "mispec_symshift_solve_block: leading dimension too small");
+    if (!S.factored)
+        throw Error(MISPEC_ELOGIC, "SparseSymShiftSolve: need to call set_shift() first");
+    const std::vector<int> widths = shiftsolve_block_plan(k, 0);
+    if (widths[0] > 1)
+        block_scratch(S);
+    int c = 0;
+    for (const int w : widths)
+    {
+        const double* X = X_dev + int64_t(c) * ldx;
+        double* Y = Y_dev + int64_t(c) * ldy;
+        if (w == 4)
+            shiftsolve_panel<4>(S, X, ldx, Y, ldy);
+        else if (w == 2)
+            shiftsolve_panel<2>(S, X, ldx, Y, ldy);
+        else
+            launch_shiftsolve(S, X, Y);
+        c += w;
     }
 }
 
@@ -2719,5 +3305,75 @@ extern "C" int mispec_symshift_solve_host(const mispec_symshift* S, const double
         launch_shiftsolve(*S, S->stage_x.p, S->stage_y.p);
         MISPEC_HIP(hipMemcpyAsync(y_host, S->stage_y.p, size_t(S->n) * sizeof(double), hipMemcpyDeviceToHost, s));
         MISPEC_HIP(hipStreamSynchronize(s));
+    });
+}
+
+// ---- block solves --------------------------------------------------------------------------------------------------------
+extern "C" int mispec_symshift_block_plan(int k, int panel, int* widths_out, int cap, int* count)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(count != nullptr, "mispec_symshift_block_plan: count is NULL");
+        const std::vector<int> widths = shiftsolve_block_plan(k, panel);
+        MISPEC_REQUIRE(int64_t(widths.size()) <= int64_t(cap < 0 ? 0 : cap) && widths_out,
+                       "mispec_symshift_block_plan: widths_out holds fewer than the " + std::to_string(widths.size()) + " panels of the plan");
+        std::copy(widths.begin(), widths.end(), widths_out);
+        *count = int(widths.size());
+    });
+}
+
+extern "C" int mispec_symshift_solve_block(const mispec_symshift* S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(S, "mispec_symshift_solve_block: NULL argument");
+        S->ctx->make_current();
+        launch_shiftsolve_block(*S, X_dev, ldx, k, Y_dev, ldy);
+    });
+}
+
+extern "C" int mispec_symshift_solve_block_host(const mispec_symshift* S, const double* X_host, int64_t ldx, int k, double* Y_host, int64_t ldy)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(S && X_host && Y_host, "mispec_symshift_solve_block_host: NULL argument");
+        MISPEC_REQUIRE(k >= 1, "mispec_symshift_solve_block_host: k < 1");
+        MISPEC_REQUIRE(ldx >= S->n && ldy >= S->n, "mispec_symshift_solve_block_host: leading dimension too small");
+        if (!S->factored)
+            throw Error(MISPEC_ELOGIC, "SparseSymShiftSolve: need to call set_shift() first");
+        S->ctx->make_current();
+        const int64_t ld = round_up(std::max<int64_t>(S->n, 1), 2);
+        if (S->stage_X.n < size_t(ld) * size_t(k))
+        {
+            S->stage_X.alloc(size_t(ld) * size_t(k));
+            S->stage_Y.alloc(size_t(ld) * size_t(k));
+        }
+        hipStream_t s = S->ctx->stream;
+        MISPEC_HIP(hipMemcpy2DAsync(S->stage_X.p, size_t(ld) * sizeof(double), X_host, size_t(ldx) * sizeof(double), size_t(S->n) * sizeof(double),
+                                    size_t(k), hipMemcpyHostToDevice, s));
+        launch_shiftsolve_block(*S, S->stage_X.p, ld, k, S->stage_Y.p, ld);
+        MISPEC_HIP(hipMemcpy2DAsync(Y_host, size_t(ldy) * sizeof(double), S->stage_Y.p, size_t(ld) * sizeof(double), size_t(S->n) * sizeof(double),
+                                    size_t(k), hipMemcpyDeviceToHost, s));
+        MISPEC_HIP(hipStreamSynchronize(s));
+    });
+}
+
+extern "C" int mispec_symshift_solve_block_time(const mispec_symshift* S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy,
+                                                int reps, float* ms_per_call)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(S && reps > 0 && ms_per_call, "mispec_symshift_solve_block_time: bad argument");
+        S->ctx->make_current();
+        launch_shiftsolve_block(*S, X_dev, ldx, k, Y_dev, ldy);  // checks the arguments, allocates the panel buffers
+        hipEvent_t e0, e1;
+        MISPEC_HIP(hipEventCreate(&e0));
+        MISPEC_HIP(hipEventCreate(&e1));
+        MISPEC_HIP(hipEventRecord(e0, S->ctx->stream));
+        for (int i = 0; i < reps; i++)
+            launch_shiftsolve_block(*S, X_dev, ldx, k, Y_dev, ldy);
+        MISPEC_HIP(hipEventRecord(e1, S->ctx->stream));
+        MISPEC_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        MISPEC_HIP(hipEventElapsedTime(&ms, e0, e1));
+        (void) hipEventDestroy(e0);
+        (void) hipEventDestroy(e1);
+        *ms_per_call = ms / float(reps);
     });
 }

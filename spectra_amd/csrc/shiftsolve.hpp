@@ -59,6 +59,10 @@ struct mispec_symshift
     std::vector<int32_t> perm_host;     // new -> old; empty: not reordered
     mispec::DevBuf<int32_t> perm_dev;
     mutable mispec::DevBuf<double> perm_x, perm_y;
+    // block solves (launch_shiftsolve_block): the panel versions of ref_r / ref_dy and perm_x / perm_y (four columns of leading
+    // dimension panel_ld) and the staging blocks of the host entry, allocated at the first use and kept
+    mutable mispec::DevBuf<double> panel_r, panel_dy, panel_px, panel_py, stage_X, stage_Y;
+    mutable int64_t panel_ld = 0;
     int64_t half_bandwidth_as_given = 0;
     bool reordered() const { return perm_dev.p != nullptr; }
     ~mispec_symshift();
@@ -67,6 +71,13 @@ struct mispec_symshift
 namespace mispec {
 // y = (A - sigma I)^{-1} x, device pointers of n doubles, enqueued on the context stream
 void launch_shiftsolve(const mispec_symshift& S, const double* x_dev, double* y_dev);
+// Y[:, c] = (A - sigma B)^{-1} X[:, c] for c < k: column-major device blocks with ldx, ldy >= n that do not overlap, enqueued on
+// the context stream.  The columns are cut into panels of 4 and 2 (option shift_block; shiftsolve_block_plan) that share one pass
+// over the factor where a panel kernel exists; every column has exactly the bits launch_shiftsolve gives for it alone.
+void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);
+// the cut of k columns: widths 4 / 2 / 1, widest first.  panel: 0 = what option shift_block says, 1 = single columns, 2 | 4 = the
+// widest panel
+std::vector<int> shiftsolve_block_plan(int k, int panel);
 // y = G^{-1} x (upper == false) / y = G^{-T} x (upper == true) for the factor G G' = A of a positive definite banded A that
 // was factored with want_cholesky and sigma = 0
 void launch_band_cholesky_solve(const mispec_symshift& S, bool upper, const double* x_dev, double* y_dev);

@@ -9,7 +9,10 @@ iteration, products with A, and HIP-event times of the solver's kernels, each as
 For orientation it also runs SymEigsSolver(nev = 8, ncv = 40, SmallestAlge) on the same operator to the same residual.
 Yardsticks: the X^H y pass of section 7.1 (0.69 of peak) and the real orthogonalisation pass (0.79 of peak).
 
-    python tools/bench_lobpcg.py [--n N] [--m M] [--no-lanczos] [--out FILE]
+--preconditioner near-band replaces Jacobi by the factorisation of the matrix's diagonals at offsets <= 3 (SparseSymShiftSolve at
+sigma = 0), applied to the active columns by the block shift solve.
+
+    python tools/bench_lobpcg.py [--n N] [--m M] [--no-lanczos] [--no-kernels] [--preconditioner jacobi|near-band] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -36,6 +39,10 @@ def main():
     ap.add_argument("--maxit", type=int, default=200)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--no-lanczos", action="store_true")
+    ap.add_argument("--no-kernels", action="store_true", help="the solve alone")
+    ap.add_argument("--preconditioner", choices=("jacobi", "near-band"), default="jacobi",
+                    help="near-band: the factorisation of the matrix's diagonals at offsets <= 3 (SparseSymShiftSolve at sigma = 0), "
+                         "applied by the block shift solve")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n, m = a.n, a.m
@@ -55,7 +62,7 @@ def main():
 
     # kernels alone (HIP events, back to back, no read-back)
     ms = C.c_float()
-    for s in (24, 63):
+    for s in (() if a.no_kernels else (24, 63)):
         U = torch.rand((s, n), dtype=torch.float64, device="cuda")
         W = torch.rand((s, n), dtype=torch.float64, device="cuda")
         torch.cuda.synchronize()
@@ -63,6 +70,23 @@ def main():
         b = 8.0 * n * 2 * s
         res["k_gram_s%d" % s] = {"ms": round(ms.value, 4), "bytes": b, "frac_8TBps": round(b / (ms.value * 1e-3) / PEAK, 3)}
         del U, W
+    if not a.no_kernels:
+        kernel_times(torch, lib, ctx, op, n, m, ms, res)
+
+    # the solve
+    pre = "jacobi"
+    if a.preconditioner == "near-band":
+        t0 = time.perf_counter()
+        near = (sp.tril(A, 0) - sp.tril(A, -4)).tocsc()  # the diagonals at offsets 0 ... 3: diagonally dominant like A, so SPD
+        pre = sa.SparseSymShiftSolve(near, ctx=ctx)
+        pre.set_shift(0.0)
+        res["seconds_preconditioner_setup"] = round(time.perf_counter() - t0, 2)
+    res["preconditioner"] = a.preconditioner
+    eigs = sa.LOBPCGSolver(op, nev=m, preconditioner=pre)
+    solve(ctx, a, eigs, op, m, res)
+
+
+def kernel_times(torch, lib, ctx, op, n, m, ms, res):
     AX = torch.rand((m, n), dtype=torch.float64, device="cuda")
     BX = torch.rand((m, n), dtype=torch.float64, device="cuda")
     R = torch.empty((m, n), dtype=torch.float64, device="cuda")
@@ -82,8 +106,8 @@ def main():
     res["block_product"] = {"ms": round(t, 4), "bytes": b, "frac_8TBps": round(b / (t * 1e-3) / PEAK, 3)}
     del AX, BX, R
 
-    # the solve
-    eigs = sa.LOBPCGSolver(op, nev=m, preconditioner="jacobi")
+
+def solve(ctx, a, eigs, op, m, res):
     ctx.sync()
     t0 = time.perf_counter()
     nconv = eigs.compute(sa.SortRule.SmallestAlge, a.maxit, a.tol)
