@@ -19,62 +19,9 @@ namespace {
 constexpr int kGemvThreads = 256;  // four rows per workgroup
 constexpr int64_t kSerialGemvEntries = 128 * 128;  // up to this many entries: storage-order row sums (k_row_gemv_serial)
 
-// VEC: row stride even and x 16-byte aligned -> double2 loads; else a scalar walk with the same reduction tree shape.
-template <bool VEC>
-__global__ __launch_bounds__(kGemvThreads) void k_row_gemv(int64_t rows, int64_t cols, int64_t ld, const double* __restrict__ M,
-                                                            const double* __restrict__ x, double* __restrict__ y)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t r = int64_t(blockIdx.x) * (kGemvThreads / 64) + (threadIdx.x >> 6);
-    if (r >= rows)
-        return;
-    const double* a = M + r * ld;
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-    if (VEC)
-    {
-        const double2* a2 = reinterpret_cast<const double2*>(a);
-        const double2* x2 = reinterpret_cast<const double2*>(x);
-        const int64_t pairs = cols >> 1;
-        int64_t p = lane;
-        for (; p + 192 < pairs; p += 256)
-        {
-            const double2 m0 = a2[p], m1 = a2[p + 64], m2 = a2[p + 128], m3 = a2[p + 192];
-            const double2 v0 = x2[p], v1 = x2[p + 64], v2 = x2[p + 128], v3 = x2[p + 192];
-            acc0 += m0.x * v0.x + m0.y * v0.y;
-            acc1 += m1.x * v1.x + m1.y * v1.y;
-            acc2 += m2.x * v2.x + m2.y * v2.y;
-            acc3 += m3.x * v3.x + m3.y * v3.y;
-        }
-        for (; p < pairs; p += 64)
-        {
-            const double2 m0 = a2[p];
-            const double2 v0 = x2[p];
-            acc0 += m0.x * v0.x + m0.y * v0.y;
-        }
-        if ((cols & 1) && lane == 0)
-            acc1 += a[cols - 1] * x[cols - 1];
-    }
-    else
-    {
-        int64_t c = lane;
-        for (; c + 192 < cols; c += 256)
-        {
-            acc0 += a[c] * x[c];
-            acc1 += a[c + 64] * x[c + 64];
-            acc2 += a[c + 128] * x[c + 128];
-            acc3 += a[c + 192] * x[c + 192];
-        }
-        for (; c < cols; c += 64)
-            acc0 += a[c] * x[c];
-    }
-    const double acc = wave_reduce_sum((acc0 + acc1) + (acc2 + acc3));
-    if (lane == 0)
-        y[r] = acc;
-}
-
 // Small matrices: one lane per row, the row summed in STORAGE ORDER with the product rounded before it is added — the order
 // of a plain CPU row-dot and of the sparse kernels (csr.hip), whose results this kernel therefore reproduces bit for bit on
-// the same entries (an entry that is 0 adds +-0).  The wavefront tree above rounds differently, which is harmless except
+// the same entries (an entry that is 0 adds +-0).  The wavefront tree of k_row_gemv rounds differently, which is harmless except
 // where a test of the reference sits exactly on a rounding boundary: test/Example1.cpp (20, 5, 12) exhausts its Krylov space
 // and the surviving noise (1e-15) lands on either side of the breakdown clamp (Lanczos.h:163-168) depending on that order.
 // A launch this small is latency-bound either way.
@@ -92,13 +39,15 @@ __global__ __launch_bounds__(64) void k_row_gemv_serial(int64_t rows, int64_t co
     y[r] = acc;
 }
 
-// k_row_gemv for a panel of K vectors: the row is read once and applied to every column.  Per column the operations of k_row_gemv
-// in its order, written out (the single kernel leaves them to the compiler's contraction; its ISA has, per 16-byte piece,
-// t = m.y * v.y rounded, t = fma(m.x, v.x, t), acc += t, an fma for the odd last column, and an fma per entry without VEC).
+// One wavefront per row, for a panel of K vectors (the single product is K = 1): the row is read once and applied to every column.
+// VEC: row stride even and every column 16-byte aligned -> double2 loads; else a scalar walk with the same reduction tree shape.
+// Per column the operations and their order do not depend on K and are written out, not left to the compiler's contraction: per
+// 16-byte piece t = m.y * v.y rounded, t = fma(m.x, v.x, t), acc += t, an fma for the odd last column, and an fma per entry
+// without VEC — every column has the bits of a single product.
 template <bool VEC, int K>
-__global__ __launch_bounds__(kGemvThreads) void k_row_gemv_panel(int64_t rows, int64_t cols, int64_t ld, const double* __restrict__ M,
-                                                                  const double* __restrict__ X, int64_t ldx, double* __restrict__ Y,
-                                                                  int64_t ldy)
+__global__ __launch_bounds__(kGemvThreads) void k_row_gemv(int64_t rows, int64_t cols, int64_t ld, const double* __restrict__ M,
+                                                            const double* __restrict__ X, int64_t ldx, double* __restrict__ Y,
+                                                            int64_t ldy)
 {
     const int lane = threadIdx.x & 63;
     const int64_t r = int64_t(blockIdx.x) * (kGemvThreads / 64) + (threadIdx.x >> 6);
@@ -191,21 +140,7 @@ namespace mispec {
 void launch_row_gemv(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t rows, int64_t cols, const double* x, double* y,
                      bool storage_order_if_small)
 {
-    if (rows <= 0)
-        return;
-    if (storage_order_if_small && rows * cols <= kSerialGemvEntries)
-    {
-        hipLaunchKernelGGL(k_row_gemv_serial, dim3(unsigned((rows + 63) / 64)), dim3(64), 0, ctx.stream, rows, cols, ld, M, x, y);
-        MISPEC_HIP(hipGetLastError());
-        return;
-    }
-    const dim3 grid(unsigned((rows + kGemvThreads / 64 - 1) / (kGemvThreads / 64))), block(kGemvThreads);
-    const bool vec = (ld % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) && (reinterpret_cast<uintptr_t>(M) % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(k_row_gemv<true>, grid, block, 0, ctx.stream, rows, cols, ld, M, x, y);
-    else
-        hipLaunchKernelGGL(k_row_gemv<false>, grid, block, 0, ctx.stream, rows, cols, ld, M, x, y);
-    MISPEC_HIP(hipGetLastError());
+    launch_row_gemv_panel(ctx, M, ld, rows, cols, x, 0, 1, y, 0, storage_order_if_small);
 }
 
 void launch_row_gemv_panel(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t rows, int64_t cols, const double* X, int64_t ldx,
@@ -213,26 +148,33 @@ void launch_row_gemv_panel(const mispec_ctx& ctx, const double* M, int64_t ld, i
 {
     if (rows <= 0 || k <= 0)
         return;
-    // the single product picks its kernel per vector from the vector's alignment: a panel kernel runs only where every column
-    // makes the same choice (an odd ldx makes every second column 8-byte aligned only), and never for the storage-order kernel
+    // a product picks its kernel per vector from the vector's alignment: a panel kernel runs only where every column makes the
+    // same choice (an odd ldx makes every second column 8-byte aligned only), and never for the storage-order kernel
     const auto vec_of = [&](int c) {
         return (ld % 2 == 0) && (reinterpret_cast<uintptr_t>(X + int64_t(c) * ldx) % 16 == 0) && (reinterpret_cast<uintptr_t>(M) % 16 == 0);
     };
+    const bool serial = storage_order_if_small && rows * cols <= kSerialGemvEntries;
     bool same = true;
     for (int c = 1; c < k; c++)
         same = same && vec_of(c) == vec_of(0);
-    if ((k != 2 && k != 4) || !same || (storage_order_if_small && rows * cols <= kSerialGemvEntries))
+    if (k != 1 && ((k != 2 && k != 4) || !same || serial))
     {
         for (int c = 0; c < k; c++)
             launch_row_gemv(ctx, M, ld, rows, cols, X + int64_t(c) * ldx, Y + int64_t(c) * ldy, storage_order_if_small);
         return;
     }
+    if (serial)
+    {
+        hipLaunchKernelGGL(k_row_gemv_serial, dim3(unsigned((rows + 63) / 64)), dim3(64), 0, ctx.stream, rows, cols, ld, M, X, Y);
+        MISPEC_HIP(hipGetLastError());
+        return;
+    }
     const dim3 grid(unsigned((rows + kGemvThreads / 64 - 1) / (kGemvThreads / 64))), block(kGemvThreads);
     const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, ctx.stream, rows, cols, ld, M, X, ldx, Y, ldy); };
     if (vec_of(0))
-        k == 4 ? launch(&k_row_gemv_panel<true, 4>) : launch(&k_row_gemv_panel<true, 2>);
+        k == 4 ? launch(&k_row_gemv<true, 4>) : k == 2 ? launch(&k_row_gemv<true, 2>) : launch(&k_row_gemv<true, 1>);
     else
-        k == 4 ? launch(&k_row_gemv_panel<false, 4>) : launch(&k_row_gemv_panel<false, 2>);
+        k == 4 ? launch(&k_row_gemv<false, 4>) : k == 2 ? launch(&k_row_gemv<false, 2>) : launch(&k_row_gemv<false, 1>);
     MISPEC_HIP(hipGetLastError());
 }
 

@@ -22,7 +22,7 @@ void launch_row_gemv(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t
                      bool storage_order_if_small = false);
 // Y[:, c] = M X[:, c] for c < k (column-major blocks): with k = 2 or 4 the matrix is read once for the panel, every column summed
 // in launch_row_gemv's order — the bits of k single products.  Any other k, columns of mixed 16-byte alignment and the
-// storage-order case are k single products.
+// storage-order case are k single products; launch_row_gemv is the case k = 1.
 void launch_row_gemv_panel(const mispec_ctx& ctx, const double* M, int64_t ld, int64_t rows, int64_t cols, const double* X, int64_t ldx,
                            int k, double* Y, int64_t ldy, bool storage_order_if_small = false);
 }  // namespace mispec

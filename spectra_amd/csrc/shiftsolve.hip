@@ -28,8 +28,10 @@
 //   * dense (n <= 4096, any sparsity — the reference's own test fixtures are of this kind): LU with partial
 //     pivoting of the dense A - sigma I on the host, explicit inverse, and a dense GEMV kernel per step.
 // Anything else (large n with large bandwidth) is rejected: a general sparse LU on the GPU is out of scope.
-// Block form (launch_shiftsolve_block): k right-hand sides in panels of 4 and 2 columns that read the factor once — panel kernels
-// for the narrow levels and the dense inverses, the single kernels per column elsewhere; every column has the bits of a single solve.
+// Every solve kernel and every host step carries the number K of right-hand sides as a template parameter: the single solve is the
+// K = 1 instantiation.  Block form (launch_shiftsolve_block): k right-hand sides in panels of 4 and 2 columns that read the factor
+// once — K = 4 and 2 for the narrow levels and the dense inverses, K = 1 per column elsewhere; every column has the bits of a single
+// solve.
 #include "shiftsolve.hpp"
 #include "reorder.hpp"
 #include "dense.hpp"
@@ -455,13 +457,19 @@ __global__ __launch_bounds__(64 * kWaveChunks) void k_chunk_solve_wave(int64_t N
 //    its use to save registers and keeps five or six in flight (s_waitcnt vmcnt(5) between the FMAs in the ISA), which makes
 //    every row wait for half a memory latency — that, not bandwidth or address arithmetic, was the 540 cycles per row.
 // Same operations in the same order as k_chunk_solve: bit-identical results.
+//
+// K right-hand sides, the columns of a column-major panel (column c of f at f + c * ldf): the single solve is K = 1, where the
+// column loops vanish.  The further columns live in registers of the same lane (hist[K][B]) and in K LDS segments; a batch of
+// factor entries is loaded once and runs K independent fma chains, which also fills the issue slots that one dependent chain
+// leaves empty.  Per column the operations and their order do not depend on K: every column has the bits of a single solve.
 constexpr int kStageThreads = 256;  // the workgroup: the sweeps run on its first wavefront, all four copy the vector in and out
-template <int B, int U>
+template <int B, int U, int K>
 __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds(int64_t N, int64_t L, ChunkStore cs, int ldl, int chunks_per_block,
                                                                    const double* __restrict__ Lf, const double* __restrict__ Dinv,
-                                                                   const double* __restrict__ f, double* __restrict__ y)
+                                                                   const double* __restrict__ f, int64_t ldf, double* __restrict__ y,
+                                                                   int64_t ldy)
 {
-    extern __shared__ double seg[];  // chunks_per_block chunks x ldl
+    extern __shared__ double seg[];  // K columns x chunks_per_block chunks x ldl
     const int64_t P = cs.P;
     const bool tail_block = blockIdx.x == gridDim.x - 1;  // the last chunk alone
     const int64_t first = tail_block ? P - 1 : int64_t(blockIdx.x) * chunks_per_block;
@@ -469,382 +477,11 @@ __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds(int64_t N, in
     const int m = int(tail_block ? N - (P - 1) * L : L - B);  // interior rows of this wavefront's chunks
     const int mr = (m + U - 1) / U * U;                        // ... in whole batches
     const int lane = threadIdx.x, nl = blockDim.x;
-    {
-        // copy in: the wavefront's rows are one contiguous piece of f; 32 loads per lane in flight, then the LDS writes
-        // (row i of the piece is row k = i mod L of chunk c = i div L, followed incrementally; separator rows are skipped)
-        const double* src = f + first * L;
-        const int64_t total = tail_block ? m : int64_t(nch) * L;
-        constexpr int kInFlight = 32;
-        int c = 0;
-        int64_t k = lane;
-        while (k >= L && !tail_block)
-        {
-            k -= L;
-            c++;
-        }
-        for (int64_t i0 = lane; i0 < total; i0 += int64_t(kInFlight) * nl)
-        {
-            double t[kInFlight];
-#pragma unroll
-            for (int q = 0; q < kInFlight; q++)
-                t[q] = (i0 + int64_t(q) * nl < total) ? src[i0 + int64_t(q) * nl] : 0.0;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < kInFlight; q++)
-            {
-                if (i0 + int64_t(q) * nl < total && k < m)
-                    seg[c * ldl + k] = t[q];
-                k += nl;
-                while (k >= L && !tail_block)
-                {
-                    k -= L;
-                    c++;
-                }
-            }
-        }
-        for (int kz = m + lane; kz < mr; kz += nl)
-            for (int cz = 0; cz < nch; cz++)
-                seg[cz * ldl + kz] = 0.0;
-    }
-    __syncthreads();
-    if (lane < nch)
-    {
-        const int64_t p = first + lane;
-        double* const zp = seg + lane * ldl;
-        const double* const lfw = Lf + cs.lf(p, 0, 0);
-        const double* const dvw = Dinv + cs.dinv(p, 0);
-        double hist[B];
-        // one batch of the forward / backward recurrence on factor entries already in registers
-        const auto forward = [&](const double (&lf)[U][B], int k0) {
-#pragma unroll
-            for (int u = 0; u < U; u++)
-            {
-                double acc = zp[k0 + u];
-#pragma unroll
-                for (int d = B - 1; d >= 0; d--)
-                    acc = fma(-lf[u][d], hist[d], acc);  // explicit: both solve kernels round identically
-#pragma unroll
-                for (int d = B - 1; d > 0; d--)
-                    hist[d] = hist[d - 1];
-                hist[0] = acc;
-                zp[k0 + u] = acc;
-            }
-        };
-        const auto backward = [&](const double (&lf)[U][B], const double (&di)[U], int k0) {  // rows k0 + U - 1 down to k0
-#pragma unroll
-            for (int u = U - 1; u >= 0; u--)
-            {
-                double acc = __dmul_rn(zp[k0 + u], di[u]);
-#pragma unroll
-                for (int d = B - 1; d >= 0; d--)
-                    acc = fma(-lf[u][d], hist[d], acc);  // explicit: both solve kernels round identically
-#pragma unroll
-                for (int d = B - 1; d > 0; d--)
-                    hist[d] = hist[d - 1];
-                hist[0] = acc;
-                zp[k0 + u] = acc;
-            }
-        };
-        // 16-byte loads: rows 2j and 2j + 1 of one entry (k0 and U are even).  A wavefront may have 63 loads outstanding,
-        // whatever their width, and with one wavefront per CU that count times the bytes per load is all the memory
-        // parallelism there is: 8-byte loads ran these sweeps at 4 TB/s.
-        const auto load_forward = [&](double (&lf)[U][B], int k0) {
-            const double* const lfk = lfw + int64_t(k0 >> 1) * (B * 128);
-#pragma unroll
-            for (int j = 0; j < U / 2; j++)
-#pragma unroll
-                for (int d = 0; d < B; d++)
-                {
-                    const double2 v = *reinterpret_cast<const double2*>(lfk + (j * B + d) * 128);
-                    lf[2 * j][d] = v.x;
-                    lf[2 * j + 1][d] = v.y;
-                }
-        };
-        const auto load_backward = [&](double (&lf)[U][B], double (&di)[U], int k0) {  // entry d of row k0 + u + d + 1
-            const double* const lfk = lfw + int64_t(k0 >> 1) * (B * 128);
-            const double* const dvk = dvw + int64_t(k0 >> 1) * 128;
-#pragma unroll
-            for (int j = U / 2 - 1; j >= 0; j--)
-            {
-                const double2 v = *reinterpret_cast<const double2*>(dvk + j * 128);
-                di[2 * j] = v.x;
-                di[2 * j + 1] = v.y;
-            }
-#pragma unroll
-            for (int d = 0; d < B; d++)
-#pragma unroll
-                for (int j = (U + d) / 2; j >= (d + 1) / 2; j--)
-                {
-                    const double2 v = *reinterpret_cast<const double2*>(lfk + (j * B + d) * 128);
-                    if (2 * j - d - 1 >= 0 && 2 * j - d - 1 < U)
-                        lf[2 * j - d - 1][d] = v.x;
-                    if (2 * j - d >= 0 && 2 * j - d < U)
-                        lf[2 * j - d][d] = v.y;
-                }
-        };
-#pragma unroll
-        for (int d = 0; d < B; d++)
-            hist[d] = 0.0;
-        for (int k0 = 0; k0 < mr; k0 += U)
-        {
-            double lf[U][B];
-            load_forward(lf, k0);
-            __builtin_amdgcn_sched_barrier(0);  // all loads of the batch are issued before the first use
-            forward(lf, k0);
-        }
-#pragma unroll
-        for (int d = 0; d < B; d++)
-            hist[d] = 0.0;
-        for (int k0 = mr - U; k0 >= 0; k0 -= U)
-        {
-            double di[U], lf[U][B];
-            load_backward(lf, di, k0);
-            __builtin_amdgcn_sched_barrier(0);
-            backward(lf, di, k0);
-        }
-    }
-    __syncthreads();
-    {
-        double* dst = y + first * L;
-        for (int k = lane; k < m; k += nl)
-        {
-#pragma unroll 8
-            for (int c = 0; c < nch; c++)
-                dst[int64_t(c) * L + k] = seg[c * ldl + k];
-        }
-    }
-}
-
-// ---- explicit inverses of the chunk interiors (levels below the top one) ------------------------------------------------
-// A lower level has few chunks (C5: 366 at the second level = 6 wavefronts of k_chunk_solve), so its two sequential sweeps are
-// pure latency: 116 us for 47 000 rows.  Its interiors are small enough to invert explicitly (m x m each, 48 MB together):
-// M_II^{-1} f becomes a batched GEMV that reads every inverse once with all lanes busy.
-//
-// k_chunk_inverse: lane (p, j) solves M_II(p) c = e_j with the chunk's banded factor and stores c as COLUMN j of the row-major
-// m x m block (ld = longest interior) — coalesced over j; the inverse is symmetric, so the GEMV below may read it either way.
-template <int B>
-__global__ __launch_bounds__(64) void k_chunk_inverse(int64_t N, int64_t L, ChunkStore cs, int64_t ld, const double* __restrict__ Lf,
-                                                      const double* __restrict__ Dinv, double* __restrict__ inv)
-{
-    const int64_t P = cs.P;
-    const int b = cs.b;
-    const int64_t p = blockIdx.y;
-    const int64_t j = int64_t(blockIdx.x) * 64 + threadIdx.x;
-    const int64_t row0 = p * L;
-    const int64_t m = ((p == P - 1) ? N : (row0 + L - b)) - row0;
-    if (j >= m)
-        return;
-    double* col = inv + size_t(p) * ld * ld + j;  // element k of the column: col[k * ld]
-    double hist[B];
-#pragma unroll
-    for (int d = 0; d < B; d++)
-        hist[d] = 0.0;
-    for (int64_t k = 0; k < m; k++)  // every lane walks all rows (zeros above row j): the factor loads are wave-uniform
-    {
-        double acc = (k == j) ? 1.0 : 0.0;
-#pragma unroll
-        for (int d = B - 1; d >= 0; d--)
-            acc -= ((d < b) ? Lf[cs.lf(p, k, d)] : 0.0) * hist[d];
-#pragma unroll
-        for (int d = B - 1; d > 0; d--)
-            hist[d] = hist[d - 1];
-        hist[0] = acc;
-        col[k * ld] = acc;
-    }
-#pragma unroll
-    for (int d = 0; d < B; d++)
-        hist[d] = 0.0;
-    for (int64_t k = m - 1; k >= 0; k--)
-    {
-        double acc = col[k * ld] * Dinv[cs.dinv(p, k)];
-#pragma unroll
-        for (int d = B - 1; d >= 0; d--)
-            acc -= ((d < b && k + d + 1 < m) ? Lf[cs.lf(p, k + d + 1, d)] : 0.0) * hist[d];
-#pragma unroll
-        for (int d = B - 1; d > 0; d--)
-            hist[d] = hist[d - 1];
-        hist[0] = acc;
-        col[k * ld] = acc;
-    }
-}
-
-// y_I(p) = inv(p) f_I(p): workgroup (p, column tile of 64), four wavefronts that each take every fourth row k of the block
-// (lane j reads inv[k][j]: 512 contiguous bytes per wavefront and row); partial sums meet in LDS in a fixed order.
-constexpr int kBlockGemvWaves = 4;
-__global__ __launch_bounds__(64 * kBlockGemvWaves) void k_block_gemv(int64_t N, int b, int64_t L, int64_t P, int64_t ld,
-                                                                      const double* __restrict__ inv, const double* __restrict__ f,
-                                                                      double* __restrict__ y)
-{
-    __shared__ double fs[256];
-    __shared__ double part[kBlockGemvWaves][64];
-    const int64_t p = blockIdx.y;
-    const int64_t row0 = p * L;
-    const int64_t m = ((p == P - 1) ? N : (row0 + L - b)) - row0;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t j = int64_t(blockIdx.x) * 64 + lane;
-    for (int64_t k = threadIdx.x; k < m; k += 64 * kBlockGemvWaves)
-        fs[k] = f[row0 + k];
-    __syncthreads();
-    const double* blk = inv + size_t(p) * ld * ld;
-    double acc = 0.0;
-    if (j < m)
-    {
-        int64_t k = w;
-        for (; k + 3 * kBlockGemvWaves < m; k += 4 * kBlockGemvWaves)
-        {
-            const double a0 = blk[k * ld + j], a1 = blk[(k + kBlockGemvWaves) * ld + j], a2 = blk[(k + 2 * kBlockGemvWaves) * ld + j],
-                         a3 = blk[(k + 3 * kBlockGemvWaves) * ld + j];
-            acc += a0 * fs[k];
-            acc += a1 * fs[k + kBlockGemvWaves];
-            acc += a2 * fs[k + 2 * kBlockGemvWaves];
-            acc += a3 * fs[k + 3 * kBlockGemvWaves];
-        }
-        for (; k < m; k += kBlockGemvWaves)
-            acc += blk[k * ld + j] * fs[k];
-    }
-    part[w][lane] = acc;
-    __syncthreads();
-    if (w == 0 && j < m)
-    {
-        double s = part[0][lane];
-#pragma unroll
-        for (int q = 1; q < kBlockGemvWaves; q++)
-            s += part[q][lane];
-        y[row0 + j] = s;
-    }
-}
-
-// separator rows: s = p*b + c  <->  global row (p+1)*L - b + c.  g[s] = f[r] - sum over interior neighbours M(r,j) y[j]
-// (all 4b operands are loaded before the first product: the kernel is a few thousand threads of pure latency)
-template <int B>
-__global__ __launch_bounds__(kThreads) void k_sep_rhs(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ band,
-                                                       const double* __restrict__ f, const double* __restrict__ y,
-                                                       double* __restrict__ g)
-{
-    const int64_t s = int64_t(blockIdx.x) * kThreads + threadIdx.x;
-    if (s >= (P - 1) * b)
-        return;
-    const int64_t p = s / b;
-    const int64_t sep0 = (p + 1) * L - b, r = sep0 + (s % b);
-    double mu[B], yu[B], ml[B], yl[B];
-#pragma unroll
-    for (int d = 1; d <= B; d++)
-    {
-        const int64_t ju = r - d;  // above: interior of chunk p unless still inside this separator
-        const bool up = d <= b && ju >= 0 && ju < sep0;
-        mu[d - 1] = up ? band[r * (b + 1) + d] : 0.0;
-        yu[d - 1] = up ? y[ju] : 0.0;
-        const int64_t jl = r + d;  // below: interior of chunk p+1 unless still inside this separator
-        const bool lo = d <= b && jl < N && jl >= sep0 + b;
-        ml[d - 1] = lo ? band[jl * (b + 1) + d] : 0.0;
-        yl[d - 1] = lo ? y[jl] : 0.0;
-    }
-    double acc = f[r];
-#pragma unroll
-    for (int d = 1; d <= B; d++)
-    {
-        if (d <= b && r - d >= 0 && r - d < sep0)
-            acc -= mu[d - 1] * yu[d - 1];
-        if (d <= b && r + d < N && r + d >= sep0 + b)
-            acc -= ml[d - 1] * yl[d - 1];
-    }
-    g[s] = acc;
-}
-
-void launch_sep_rhs(hipStream_t stream, int64_t N, int b, int64_t L, int64_t P, const double* band, const double* f, const double* y,
-                    double* g)
-{
-    const dim3 grid(unsigned(((P - 1) * b + kThreads - 1) / kThreads));
-    if (b <= 4)
-        hipLaunchKernelGGL(k_sep_rhs<4>, grid, dim3(kThreads), 0, stream, N, b, L, P, band, f, y, g);
-    else if (b <= 8)
-        hipLaunchKernelGGL(k_sep_rhs<8>, grid, dim3(kThreads), 0, stream, N, b, L, P, band, f, y, g);
-    else if (b <= 16)
-        hipLaunchKernelGGL(k_sep_rhs<16>, grid, dim3(kThreads), 0, stream, N, b, L, P, band, f, y, g);
-    else
-        hipLaunchKernelGGL(k_sep_rhs<64>, grid, dim3(kThreads), 0, stream, N, b, L, P, band, f, y, g);
-}
-
-// x_I = y_I - W [x_S(p-1); x_S(p)], x_S copied into place.  W: 2b columns of N (column c of row r at c*N + r; zero in
-// separator rows): one workgroup per chunk, so the 2b separator unknowns are wave-uniform (scalar loads) and every W / y / x
-// access is a coalesced line.  (The first version — one thread per row over a row-major W, chunk number by a 64-bit division —
-// ran at 3.6 TB/s.)
-constexpr int kBackThreads = 128;
-constexpr int64_t kBackPiece = 2048;  // rows per workgroup
-__global__ __launch_bounds__(kBackThreads) void k_back_subst(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ W,
-                                                             const double* __restrict__ y, const double* __restrict__ xs,
-                                                             double* __restrict__ x)
-{
-    const int64_t p = blockIdx.x;
-    const int64_t row0 = p * L;
-    const int64_t end = (p == P - 1) ? N : row0 + L;
-    const int64_t sep0 = (p == P - 1) ? N : row0 + L - b;
-    const double* const xprev = xs + (p - 1) * b;  // p > 0
-    const double* const xnext = xs + p * b;        // p < P - 1
-    // blockIdx.y: pieces of kBackPiece rows of a long chunk (wide bands: up to 31250 rows in at most 32 chunks — one workgroup per
-    // chunk streamed its 2b columns of W through 128 threads: 12 ms at n = 1e6, b = 64)
-    const int64_t piece0 = row0 + int64_t(blockIdx.y) * kBackPiece;
-    const int64_t piece1 = (piece0 + kBackPiece < end) ? piece0 + kBackPiece : end;
-    for (int64_t r = piece0 + threadIdx.x; r < piece1; r += kBackThreads)
-    {
-        if (r >= sep0)
-        {
-            x[r] = xnext[r - sep0];
-            continue;
-        }
-        double acc = y[r];
-        // eight columns of W in flight per thread (a plain loop over the columns waits for every load in turn: 0.8 ms for the
-        // 512 MB of W at n = 1e6, b = 32); the products enter in column order as before
-        const auto side = [&](const double* Wc, const double* xv) {
-            int c = 0;
-            for (; c + 8 <= b; c += 8)
-            {
-                double w[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    w[i] = Wc[int64_t(c + i) * N];
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    acc -= w[i] * xv[c + i];
-            }
-            for (; c < b; c++)
-                acc -= Wc[int64_t(c) * N] * xv[c];
-        };
-        if (p > 0)
-            side(W + r, xprev);
-        if (p < P - 1)
-            side(W + int64_t(b) * N + r, xnext);
-        x[r] = acc;
-    }
-}
-
-// ---- panel forms: K right-hand sides per pass over the factor (launch_shiftsolve_block) ------------------------------------
-// Every kernel below reads what its single-vector counterpart reads ONCE and applies it to the K columns of a column-major panel
-// (column c of f at f + c * ldf, ...).  Per column the operations and their order are the counterpart's, written out with fma()
-// where the counterpart's ISA has v_fma_f64 (the compiler contracts every `acc += a * x` / `acc -= w * x` of k_block_gemv,
-// k_sep_rhs and k_back_subst; none keeps a rounded product): column c of the result has the bits of a single solve.
-
-// k_chunk_solve_lds for K columns: the further columns live in registers of the same lane (hist[K][B]) and in K LDS segments; a
-// batch of factor entries is loaded once and runs K independent fma chains, which also fills the issue slots that the one
-// dependent chain of the single kernel leaves empty.  Loop bounds stay wave-uniform and the scheduling barrier stays between a
-// batch's loads and its recurrences, for the reasons given above k_chunk_solve_lds.
-template <int B, int U, int K>
-__global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t N, int64_t L, ChunkStore cs, int ldl, int chunks_per_block,
-                                                                         const double* __restrict__ Lf, const double* __restrict__ Dinv,
-                                                                         const double* __restrict__ f, int64_t ldf, double* __restrict__ y,
-                                                                         int64_t ldy)
-{
-    extern __shared__ double seg[];  // K columns x chunks_per_block chunks x ldl
-    const int64_t P = cs.P;
-    const bool tail_block = blockIdx.x == gridDim.x - 1;  // the last chunk alone
-    const int64_t first = tail_block ? P - 1 : int64_t(blockIdx.x) * chunks_per_block;
-    const int nch = tail_block ? 1 : int(min(int64_t(chunks_per_block), P - 1 - first));
-    const int m = int(tail_block ? N - (P - 1) * L : L - B);
-    const int mr = (m + U - 1) / U * U;
-    const int lane = threadIdx.x, nl = blockDim.x;
     const int cstride = chunks_per_block * ldl;  // doubles per column of the panel
     for (int col = 0; col < K; col++)
     {
+        // copy in: the wavefront's rows are one contiguous piece of f; 32 loads per lane in flight, then the LDS writes
+        // (row i of the piece is row k = i mod L of chunk c = i div L, followed incrementally; separator rows are skipped)
         double* const sc = seg + col * cstride;
         const double* src = f + int64_t(col) * ldf + first * L;
         const int64_t total = tail_block ? m : int64_t(nch) * L;
@@ -888,6 +525,7 @@ __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t
         const double* const lfw = Lf + cs.lf(p, 0, 0);
         const double* const dvw = Dinv + cs.dinv(p, 0);
         double hist[K][B];
+        // one batch of the forward / backward recurrence on factor entries already in registers
         const auto forward = [&](const double (&lf)[U][B], int k0) {
 #pragma unroll
             for (int u = 0; u < U; u++)
@@ -898,7 +536,7 @@ __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t
                     double acc = zp[c * cstride + k0 + u];
 #pragma unroll
                     for (int d = B - 1; d >= 0; d--)
-                        acc = fma(-lf[u][d], hist[c][d], acc);
+                        acc = fma(-lf[u][d], hist[c][d], acc);  // explicit: both solve kernels round identically
 #pragma unroll
                     for (int d = B - 1; d > 0; d--)
                         hist[c][d] = hist[c][d - 1];
@@ -917,7 +555,7 @@ __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t
                     double acc = __dmul_rn(zp[c * cstride + k0 + u], di[u]);
 #pragma unroll
                     for (int d = B - 1; d >= 0; d--)
-                        acc = fma(-lf[u][d], hist[c][d], acc);
+                        acc = fma(-lf[u][d], hist[c][d], acc);  // explicit: both solve kernels round identically
 #pragma unroll
                     for (int d = B - 1; d > 0; d--)
                         hist[c][d] = hist[c][d - 1];
@@ -926,6 +564,9 @@ __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t
                 }
             }
         };
+        // 16-byte loads: rows 2j and 2j + 1 of one entry (k0 and U are even).  A wavefront may have 63 loads outstanding,
+        // whatever their width, and with one wavefront per CU that count times the bytes per load is all the memory
+        // parallelism there is: 8-byte loads ran these sweeps at 4 TB/s.
         const auto load_forward = [&](double (&lf)[U][B], int k0) {
             const double* const lfk = lfw + int64_t(k0 >> 1) * (B * 128);
 #pragma unroll
@@ -999,11 +640,68 @@ __global__ __launch_bounds__(kStageThreads) void k_chunk_solve_lds_panel(int64_t
     }
 }
 
-// k_block_gemv for K columns: binv is read once per panel; per column the same partial sum per wavefront and the same combination
+// ---- explicit inverses of the chunk interiors (levels below the top one) ------------------------------------------------
+// A lower level has few chunks (C5: 366 at the second level = 6 wavefronts of k_chunk_solve), so its two sequential sweeps are
+// pure latency: 116 us for 47 000 rows.  Its interiors are small enough to invert explicitly (m x m each, 48 MB together):
+// M_II^{-1} f becomes a batched GEMV that reads every inverse once with all lanes busy.
+//
+// k_chunk_inverse: lane (p, j) solves M_II(p) c = e_j with the chunk's banded factor and stores c as COLUMN j of the row-major
+// m x m block (ld = longest interior) — coalesced over j; the inverse is symmetric, so the GEMV below may read it either way.
+template <int B>
+__global__ __launch_bounds__(64) void k_chunk_inverse(int64_t N, int64_t L, ChunkStore cs, int64_t ld, const double* __restrict__ Lf,
+                                                      const double* __restrict__ Dinv, double* __restrict__ inv)
+{
+    const int64_t P = cs.P;
+    const int b = cs.b;
+    const int64_t p = blockIdx.y;
+    const int64_t j = int64_t(blockIdx.x) * 64 + threadIdx.x;
+    const int64_t row0 = p * L;
+    const int64_t m = ((p == P - 1) ? N : (row0 + L - b)) - row0;
+    if (j >= m)
+        return;
+    double* col = inv + size_t(p) * ld * ld + j;  // element k of the column: col[k * ld]
+    double hist[B];
+#pragma unroll
+    for (int d = 0; d < B; d++)
+        hist[d] = 0.0;
+    for (int64_t k = 0; k < m; k++)  // every lane walks all rows (zeros above row j): the factor loads are wave-uniform
+    {
+        double acc = (k == j) ? 1.0 : 0.0;
+#pragma unroll
+        for (int d = B - 1; d >= 0; d--)
+            acc -= ((d < b) ? Lf[cs.lf(p, k, d)] : 0.0) * hist[d];
+#pragma unroll
+        for (int d = B - 1; d > 0; d--)
+            hist[d] = hist[d - 1];
+        hist[0] = acc;
+        col[k * ld] = acc;
+    }
+#pragma unroll
+    for (int d = 0; d < B; d++)
+        hist[d] = 0.0;
+    for (int64_t k = m - 1; k >= 0; k--)
+    {
+        double acc = col[k * ld] * Dinv[cs.dinv(p, k)];
+#pragma unroll
+        for (int d = B - 1; d >= 0; d--)
+            acc -= ((d < b && k + d + 1 < m) ? Lf[cs.lf(p, k + d + 1, d)] : 0.0) * hist[d];
+#pragma unroll
+        for (int d = B - 1; d > 0; d--)
+            hist[d] = hist[d - 1];
+        hist[0] = acc;
+        col[k * ld] = acc;
+    }
+}
+
+// y_I(p) = inv(p) f_I(p): workgroup (p, column tile of 64), four wavefronts that each take every fourth row k of the block
+// (lane j reads inv[k][j]: 512 contiguous bytes per wavefront and row); partial sums meet in LDS in a fixed order.
+// K columns of a column-major panel: the inverse is read once for all of them; per column the same partial sum per wavefront and
+// the same combination whatever K is.
+constexpr int kBlockGemvWaves = 4;
 template <int K>
-__global__ __launch_bounds__(64 * kBlockGemvWaves) void k_block_gemv_panel(int64_t N, int b, int64_t L, int64_t P, int64_t ld,
-                                                                            const double* __restrict__ inv, const double* __restrict__ f,
-                                                                            int64_t ldf, double* __restrict__ y, int64_t ldy)
+__global__ __launch_bounds__(64 * kBlockGemvWaves) void k_block_gemv(int64_t N, int b, int64_t L, int64_t P, int64_t ld,
+                                                                      const double* __restrict__ inv, const double* __restrict__ f,
+                                                                      int64_t ldf, double* __restrict__ y, int64_t ldy)
 {
     __shared__ double fs[K][256];
     __shared__ double part[K][kBlockGemvWaves][64];
@@ -1064,11 +762,13 @@ __global__ __launch_bounds__(64 * kBlockGemvWaves) void k_block_gemv_panel(int64
     }
 }
 
-// k_sep_rhs for K columns: the band rows of a separator row are loaded once
+// separator rows: s = p*b + c  <->  global row (p+1)*L - b + c.  g[s] = f[r] - sum over interior neighbours M(r,j) y[j]
+// (the operands are loaded before the first product: the kernel is a few thousand threads of pure latency).  K columns of a
+// column-major panel: the band rows of a separator row are loaded once, then per column its y values and one fma chain.
 template <int B, int K>
-__global__ __launch_bounds__(kThreads) void k_sep_rhs_panel(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ band,
-                                                             const double* __restrict__ f, int64_t ldf, const double* __restrict__ y,
-                                                             int64_t ldy, double* __restrict__ g, int64_t ldg)
+__global__ __launch_bounds__(kThreads) void k_sep_rhs(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ band,
+                                                       const double* __restrict__ f, int64_t ldf, const double* __restrict__ y,
+                                                       int64_t ldy, double* __restrict__ g, int64_t ldg)
 {
     const int64_t s = int64_t(blockIdx.x) * kThreads + threadIdx.x;
     if (s >= (P - 1) * b)
@@ -1079,10 +779,10 @@ __global__ __launch_bounds__(kThreads) void k_sep_rhs_panel(int64_t N, int b, in
 #pragma unroll
     for (int d = 1; d <= B; d++)
     {
-        const int64_t ju = r - d;
+        const int64_t ju = r - d;  // above: interior of chunk p unless still inside this separator
         const bool up = d <= b && ju >= 0 && ju < sep0;
         mu[d - 1] = up ? band[r * (b + 1) + d] : 0.0;
-        const int64_t jl = r + d;
+        const int64_t jl = r + d;  // below: interior of chunk p+1 unless still inside this separator
         const bool lo = d <= b && jl < N && jl >= sep0 + b;
         ml[d - 1] = lo ? band[jl * (b + 1) + d] : 0.0;
     }
@@ -1111,11 +811,17 @@ __global__ __launch_bounds__(kThreads) void k_sep_rhs_panel(int64_t N, int b, in
     }
 }
 
-// k_back_subst for K columns: W is read once per panel, the 2b separator unknowns of every column stay wave-uniform operands
+// x_I = y_I - W [x_S(p-1); x_S(p)], x_S copied into place.  W: 2b columns of N (column c of row r at c*N + r; zero in
+// separator rows): one workgroup per chunk, so the 2b separator unknowns are wave-uniform (scalar loads) and every W / y / x
+// access is a coalesced line.  (The first version — one thread per row over a row-major W, chunk number by a 64-bit division —
+// ran at 3.6 TB/s.)  K columns of a column-major panel: W is read once for all of them, and the 2b separator unknowns of every
+// column stay wave-uniform operands.
+constexpr int kBackThreads = 128;
+constexpr int64_t kBackPiece = 2048;  // rows per workgroup
 template <int K>
-__global__ __launch_bounds__(kBackThreads) void k_back_subst_panel(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ W,
-                                                                   const double* __restrict__ y, int64_t ldy, const double* __restrict__ xs,
-                                                                   int64_t ldxs, double* __restrict__ x, int64_t ldx)
+__global__ __launch_bounds__(kBackThreads) void k_back_subst(int64_t N, int b, int64_t L, int64_t P, const double* __restrict__ W,
+                                                             const double* __restrict__ y, int64_t ldy, const double* __restrict__ xs,
+                                                             int64_t ldxs, double* __restrict__ x, int64_t ldx)
 {
     const int64_t p = blockIdx.x;
     const int64_t row0 = p * L;
@@ -1123,6 +829,8 @@ __global__ __launch_bounds__(kBackThreads) void k_back_subst_panel(int64_t N, in
     const int64_t sep0 = (p == P - 1) ? N : row0 + L - b;
     const double* const xprev = xs + (p - 1) * b;  // p > 0
     const double* const xnext = xs + p * b;        // p < P - 1
+    // blockIdx.y: pieces of kBackPiece rows of a long chunk (wide bands: up to 31250 rows in at most 32 chunks — one workgroup per
+    // chunk streamed its 2b columns of W through 128 threads: 12 ms at n = 1e6, b = 64)
     const int64_t piece0 = row0 + int64_t(blockIdx.y) * kBackPiece;
     const int64_t piece1 = (piece0 + kBackPiece < end) ? piece0 + kBackPiece : end;
     for (int64_t r = piece0 + threadIdx.x; r < piece1; r += kBackThreads)
@@ -1138,6 +846,8 @@ __global__ __launch_bounds__(kBackThreads) void k_back_subst_panel(int64_t N, in
 #pragma unroll
         for (int c = 0; c < K; c++)
             acc[c] = y[int64_t(c) * ldy + r];
+        // eight columns of W in flight per thread (a plain loop over the columns waits for every load in turn: 0.8 ms for the
+        // 512 MB of W at n = 1e6, b = 32); the products enter in column order as before
         const auto side = [&](const double* Wc, const double* xv) {
             int q = 0;
             for (; q + 8 <= b; q += 8)
@@ -1169,6 +879,9 @@ __global__ __launch_bounds__(kBackThreads) void k_back_subst_panel(int64_t N, in
             x[int64_t(c) * ldx + r] = acc[c];
     }
 }
+
+// Per column every kernel above does the same operations in the same order whatever K is, written out with fma() / __dmul_rn() /
+// __dadd_rn() and not left to the compiler's contraction: column c of a panel has the bits of a single solve.
 
 // dst = src with sigma subtracted from the diagonal entries (column 0 of the n x (b+1) row-major band)
 // (pencil: dst = src - sigma * srcB entry by entry, the bands share one layout)
@@ -2131,10 +1844,99 @@ int solve_lanes(int64_t P)
     return knob ? knob : kChunkThreads;
 }
 
-void launch_chunk_solve(const mispec_ctx& ctx, const BandLevel& lev, dim3 grid_unused, const double* f, double* y, int mode = 0,
-                        double* u_out = nullptr)
+// ---- a level for K right-hand sides: the single solve is K = 1, the block solve runs panels of K = 2 and 4 columns -----------
+// A panel step takes its K-column kernel where one is instantiated — the narrow levels (half-bandwidth <= 8) and the dense last
+// level — and otherwise the K = 1 kernel column by column on the same panel buffers, so a wide level in the middle of the
+// recursion (b = 8 has a Schur band of 15) loops while the levels around it run as panels.
+constexpr int kMaxPanel = 4;
+// Sweeps of a panel of 4 at half-bandwidths up to this run as two launches of the 2-column kernel (64 chunks per workgroup, batches of
+// 32 rows): the 4-column kernel there (32 chunks per workgroup, 200 registers parked in AGPRs) measured 0.0637 against 0.0607 ms per
+// column at n = 2e6, b = 3, while at b = 8 it is the faster one (0.130 against 0.160; DESIGN.md 3.5)
+constexpr int kSweepPairsUpTo = 4;
+
+// What a level's steps write between them: the level's own vectors for K = 1, the panel buffers (column-major, leading dimensions
+// pld / pld_s; panel_scratch) for K = 2 and 4.
+struct LevelScratch
 {
-    (void) grid_unused;
+    double *y, *g, *xs;
+    int64_t ldy, lds;  // of y, and of g and xs
+};
+template <int K>
+LevelScratch level_scratch(const BandLevel& lev)
+{
+    if (K == 1)
+        return {lev.y.p, lev.g.p, lev.xs.p, 0, 0};
+    return {lev.py.p, lev.pg.p, lev.pxs.p, lev.pld, lev.pld_s};
+}
+
+void panel_scratch(const BandLevel& top)
+{
+    for (const BandLevel* l = &top; l && l->P > 1; l = l->next.get())
+        if (!l->py.p)
+        {
+            l->pld = round_up(l->N, 2);  // even: every column 16-byte aligned, like the single solve's own buffers
+            l->pld_s = round_up((l->P - 1) * l->b, 2);
+            l->py.alloc(size_t(l->pld) * kMaxPanel);
+            l->pg.alloc(size_t(l->pld_s) * kMaxPanel);
+            l->pxs.alloc(size_t(l->pld_s) * kMaxPanel);
+        }
+}
+
+// The instantiations of the staged sweep: K = 1 with every batch length (test hook MISPEC_SHIFT=batch=8|16|32), a panel with the
+// batch length its half-bandwidth fixes.
+template <int B, int K>
+auto lds_sweep_kernel(int U)
+{
+    if constexpr (K == 1)
+        return U == 32 ? &k_chunk_solve_lds<B, 32, 1> : U == 16 ? &k_chunk_solve_lds<B, 16, 1> : &k_chunk_solve_lds<B, 8, 1>;
+    else
+        return &k_chunk_solve_lds<B, (B <= 4 ? 32 : 16), K>;
+}
+
+// The LDS-staged interior sweeps of a narrow level for K columns (MISPEC_SHIFT=lds=0: never); false, and nothing launched: this
+// level, under the options in force, has no staged kernel for K columns or its segments do not fit the LDS.
+template <int K>
+bool launch_chunk_solve_lds(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, double* y, int64_t ldy)
+{
+    const ShiftOptions so = shift_options();
+    if (lev.cs.wide || so.lds == 0 || lev.P <= 1 || lev.b < 1 || lev.b > 8)
+        return false;
+    const int U_of_b = lev.b <= 4 ? 32 : 16;
+    const int U = so.batch ? so.batch : U_of_b;
+    if (K > 1 && U != U_of_b)
+        return false;
+    // K columns of a 64-chunk workgroup do not fit the LDS of a CU (66 KB each): fewer chunks per workgroup for wider panels
+    const int chunks = std::min(solve_lanes(lev.P), K == 4 ? 32 : 64);
+    const auto whole = [U](int64_t m) { return (m + U - 1) / U * U; };
+    // LDS row stride of a chunk: the padded interior; the last chunk's (its workgroup holds it alone) may spread over all rows
+    const int64_t ldl = std::max<int64_t>(whole(lev.L - lev.b), (whole(lev.N - (lev.P - 1) * lev.L) + chunks - 1) / chunks) | 1;
+    const size_t lds_bytes = size_t(K) * size_t(chunks) * size_t(ldl) * sizeof(double);
+    if (lds_bytes > 160 * 1024)
+        return false;
+    const dim3 grid(unsigned((lev.P - 1 + chunks - 1) / chunks) + 1);  // + the last chunk's own workgroup
+    const auto launch = [&](auto kernel) {
+        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+        hipLaunchKernelGGL(kernel, grid, dim3(kStageThreads), lds_bytes, ctx.stream, lev.N, lev.L, lev.cs, int(ldl), chunks, lev.Lf.p,
+                           lev.Dinv.p, f, ldf, y, ldy);
+    };
+    switch (lev.b)
+    {
+        case 1: launch(lds_sweep_kernel<1, K>(U)); break;
+        case 2: launch(lds_sweep_kernel<2, K>(U)); break;
+        case 3: launch(lds_sweep_kernel<3, K>(U)); break;
+        case 4: launch(lds_sweep_kernel<4, K>(U)); break;
+        case 5: launch(lds_sweep_kernel<5, K>(U)); break;
+        case 6: launch(lds_sweep_kernel<6, K>(U)); break;
+        case 7: launch(lds_sweep_kernel<7, K>(U)); break;
+        case 8: launch(lds_sweep_kernel<8, K>(U)); break;
+    }
+    MISPEC_HIP(hipGetLastError());
+    return true;
+}
+
+// the interior sweeps of a level for one vector: modes and u_out as k_chunk_solve
+void launch_chunk_solve(const mispec_ctx& ctx, const BandLevel& lev, const double* f, double* y, int mode = 0, double* u_out = nullptr)
+{
     if (lev.cs.wide)  // half-bandwidth 9...64 on the row-major layout: one wavefront per chunk
     {
         hipLaunchKernelGGL(k_chunk_solve_wave, dim3(unsigned((lev.P + kWaveChunks - 1) / kWaveChunks)), dim3(64 * kWaveChunks), 0, ctx.stream,
@@ -2142,52 +1944,11 @@ void launch_chunk_solve(const mispec_ctx& ctx, const BandLevel& lev, dim3 grid_u
         MISPEC_HIP(hipGetLastError());
         return;
     }
+    // plain solves of a level whose wavefront segments fit the LDS: the staged kernel
+    if (mode == 0 && u_out == nullptr && launch_chunk_solve_lds<1>(ctx, lev, f, 0, y, 0))
+        return;
     const int lanes = solve_lanes(lev.P);
     const dim3 grid(unsigned((lev.P - 1 + lanes - 1) / lanes) + 1);  // + the last chunk's own workgroup
-    const bool chol = mode != 0 || u_out != nullptr;
-    // plain solves of a level whose wavefront segments fit the LDS: the staged kernel (MISPEC_SHIFT=lds=0: always the general one)
-    const ShiftOptions so = shift_options();
-    if (!chol && so.lds != 0 && lev.P > 1 && lev.b >= 1 && lev.b <= 8)
-    {
-        const int U = so.batch ? so.batch : (lev.b <= 4 ? 32 : 16);
-        const auto whole = [U](int64_t m) { return (m + U - 1) / U * U; };
-        // LDS row stride of a chunk: the padded interior; the last chunk's (its workgroup holds it alone) may spread over all rows
-        const int64_t ldl = std::max<int64_t>(whole(lev.L - lev.b), (whole(lev.N - (lev.P - 1) * lev.L) + lanes - 1) / lanes) | 1;
-        const size_t lds_bytes = size_t(lanes) * size_t(ldl) * sizeof(double);
-        if (lds_bytes <= 160 * 1024)
-        {
-            const auto launch = [&](auto kernel) {
-                MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               int(lds_bytes)));
-                hipLaunchKernelGGL(kernel, grid, dim3(kStageThreads), lds_bytes, ctx.stream, lev.N, lev.L, lev.cs, int(ldl), lanes, lev.Lf.p,
-                                   lev.Dinv.p, f, y);
-            };
-#define MISPEC_LDS_CASE(B)                       \
-    case B:                                      \
-        if (U == 32)                             \
-            launch(&k_chunk_solve_lds<B, 32>);   \
-        else if (U == 16)                        \
-            launch(&k_chunk_solve_lds<B, 16>);   \
-        else                                     \
-            launch(&k_chunk_solve_lds<B, 8>);    \
-        break
-            switch (lev.b)
-            {
-                MISPEC_LDS_CASE(1);
-                MISPEC_LDS_CASE(2);
-                MISPEC_LDS_CASE(3);
-                MISPEC_LDS_CASE(4);
-                MISPEC_LDS_CASE(5);
-                MISPEC_LDS_CASE(6);
-                MISPEC_LDS_CASE(7);
-                MISPEC_LDS_CASE(8);
-            }
-#undef MISPEC_LDS_CASE
-            MISPEC_HIP(hipGetLastError());
-            return;
-        }
-    }
-    (void) chol;
 #define MISPEC_CHUNK(B, U) \
     hipLaunchKernelGGL((k_chunk_solve<B, U>), grid, dim3(unsigned(lanes)), 0, ctx.stream, lev.N, lev.L, lev.cs, lev.Lf.p, lev.Dinv.p, f, y, mode, u_out)
     // U rows of factor entries are in flight per lane and batch ((B + 2) * U doubles): as deep as the register file allows
@@ -2205,152 +1966,79 @@ void launch_chunk_solve(const mispec_ctx& ctx, const BandLevel& lev, dim3 grid_u
     MISPEC_HIP(hipGetLastError());
 }
 
-void solve_level(const mispec_ctx& ctx, const BandLevel& lev, const double* f, double* x)
+// g_S = f_S - M_SI y_I for K columns; panels have the kernel of the narrow levels only, a wider level runs its columns in turn
+template <int K>
+void launch_sep_rhs(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, const double* y, int64_t ldy, double* g,
+                    int64_t ldg)
 {
+    const dim3 grid(unsigned(((lev.P - 1) * lev.b + kThreads - 1) / kThreads));
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, ldf, y, ldy, g, ldg);
+    };
+    if (lev.b <= 4)
+        launch(&k_sep_rhs<4, K>);
+    else if (lev.b <= 8)
+        launch(&k_sep_rhs<8, K>);
+    else if constexpr (K == 1)
+        lev.b <= 16 ? launch(&k_sep_rhs<16, 1>) : launch(&k_sep_rhs<64, 1>);
+    else
+        for (int c = 0; c < K; c++)
+            launch_sep_rhs<1>(ctx, lev, f + c * ldf, 0, y + c * ldy, 0, g + c * ldg, 0);
+    MISPEC_HIP(hipGetLastError());
+}
+
+// x_I = y_I - W x_S for K columns, with the same rule
+template <int K>
+void launch_back_subst(const mispec_ctx& ctx, const BandLevel& lev, const double* y, int64_t ldy, const double* xs, int64_t ldxs, double* x,
+                       int64_t ldx)
+{
+    if (K > 1 && lev.b > 8)
+    {
+        for (int c = 0; c < K; c++)
+            launch_back_subst<1>(ctx, lev, y + c * ldy, 0, xs + c * ldxs, 0, x + c * ldx, 0);
+        return;
+    }
+    const int64_t longest = std::max<int64_t>(lev.L, lev.N - (lev.P - 1) * lev.L);
+    hipLaunchKernelGGL(k_back_subst<K>, dim3(unsigned(lev.P), unsigned((longest + kBackPiece - 1) / kBackPiece)), dim3(kBackThreads), 0,
+                       ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, y, ldy, xs, ldxs, x, ldx);
+    MISPEC_HIP(hipGetLastError());
+}
+
+template <int K>
+void solve_level(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, double* x, int64_t ldx)
+{
+    const auto sweep_by_column = [&](double* y, int64_t ldy) {
+        for (int c = 0; c < K; c++)
+            launch_chunk_solve(ctx, lev, f + c * ldf, y + c * ldy);
+    };
     if (lev.P == 1)
     {
         if (lev.inv.p)
         {
             // explicit inverse, row-major: one wavefront per row (dense.hip) — n waves in flight instead of n/256
             // workgroups that each walk all the columns (the first version: 233 us at n = 1830, a third of a banded solve)
-            launch_row_gemv(ctx, lev.inv.p, lev.N, lev.N, lev.N, f, x);
-        }
-        else
-            launch_chunk_solve(ctx, lev, dim3(1), f, x);
-        return;
-    }
-    if (lev.binv.p)
-    {
-        hipLaunchKernelGGL(k_block_gemv, dim3(unsigned((lev.binv_ld + 63) / 64), unsigned(lev.P)), dim3(64 * kBlockGemvWaves), 0,
-                           ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.binv_ld, lev.binv.p, f, lev.y.p);
-        MISPEC_HIP(hipGetLastError());
-    }
-    else
-        launch_chunk_solve(ctx, lev, dim3(unsigned((lev.P + kChunkThreads - 1) / kChunkThreads)), f, lev.y.p);
-    launch_sep_rhs(ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, lev.y.p, lev.g.p);
-    MISPEC_HIP(hipGetLastError());
-    solve_level(ctx, *lev.next, lev.g.p, lev.xs.p);
-    {
-        const int64_t longest = std::max<int64_t>(lev.L, lev.N - (lev.P - 1) * lev.L);
-        hipLaunchKernelGGL(k_back_subst, dim3(unsigned(lev.P), unsigned((longest + kBackPiece - 1) / kBackPiece)), dim3(kBackThreads), 0,
-                           ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, lev.y.p, lev.xs.p, x);
-    }
-    MISPEC_HIP(hipGetLastError());
-}
-
-// ---- a level for a panel of K = 2 or 4 columns (launch_shiftsolve_block) ---------------------------------------------------------
-// Each step takes its panel kernel where there is one — the narrow levels (half-bandwidth <= 8, not cs.wide) and the dense last
-// level — and otherwise the single-vector kernel column by column on the same panel buffers, so a wide level in the middle of the
-// recursion (b = 8 has a Schur band of 15) loops while the levels around it run as panels.
-constexpr int kMaxPanel = 4;
-// Sweeps of a panel of 4 at half-bandwidths up to this run as two launches of the 2-column kernel (64 chunks per workgroup, batches of
-// 32 rows): the 4-column kernel there (32 chunks per workgroup, 200 registers parked in AGPRs) measured 0.0637 against 0.0607 ms per
-// column at n = 2e6, b = 3, while at b = 8 it is the faster one (0.130 against 0.160; DESIGN.md 3.5)
-constexpr int kSweepPairsUpTo = 4;
-
-void panel_scratch(const BandLevel& top)
-{
-    for (const BandLevel* l = &top; l && l->P > 1; l = l->next.get())
-        if (!l->py.p)
-        {
-            l->pld = round_up(l->N, 2);  // even: every column 16-byte aligned, like the single solve's own buffers
-            l->pld_s = round_up((l->P - 1) * l->b, 2);
-            l->py.alloc(size_t(l->pld) * kMaxPanel);
-            l->pg.alloc(size_t(l->pld_s) * kMaxPanel);
-            l->pxs.alloc(size_t(l->pld_s) * kMaxPanel);
-        }
-}
-
-// the interior sweeps of a narrow level for K columns; false: no panel kernel for this level under the options in force
-template <int K>
-bool launch_chunk_solve_panel(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, double* y, int64_t ldy)
-{
-    const ShiftOptions so = shift_options();
-    const int U = lev.b <= 4 ? 32 : 16;
-    if (lev.cs.wide || so.lds == 0 || lev.P <= 1 || lev.b < 1 || lev.b > 8 || (so.batch != 0 && so.batch != U))
-        return false;
-    // K columns of a 64-chunk workgroup do not fit the LDS of a CU (66 KB each): fewer chunks per workgroup for wider panels
-    int chunks = std::min(solve_lanes(lev.P), K == 4 ? 32 : 64);
-    const auto whole = [U](int64_t m) { return (m + U - 1) / U * U; };
-    const int64_t ldl = std::max<int64_t>(whole(lev.L - lev.b), (whole(lev.N - (lev.P - 1) * lev.L) + chunks - 1) / chunks) | 1;
-    const size_t lds_bytes = size_t(K) * size_t(chunks) * size_t(ldl) * sizeof(double);
-    if (lds_bytes > 160 * 1024)
-        return false;
-    const dim3 grid(unsigned((lev.P - 1 + chunks - 1) / chunks) + 1);  // + the last chunk's own workgroup
-    const auto launch = [&](auto kernel) {
-        MISPEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
-        hipLaunchKernelGGL(kernel, grid, dim3(kStageThreads), lds_bytes, ctx.stream, lev.N, lev.L, lev.cs, int(ldl), chunks, lev.Lf.p,
-                           lev.Dinv.p, f, ldf, y, ldy);
-    };
-    switch (lev.b)
-    {
-        case 1: launch(&k_chunk_solve_lds_panel<1, 32, K>); break;
-        case 2: launch(&k_chunk_solve_lds_panel<2, 32, K>); break;
-        case 3: launch(&k_chunk_solve_lds_panel<3, 32, K>); break;
-        case 4: launch(&k_chunk_solve_lds_panel<4, 32, K>); break;
-        case 5: launch(&k_chunk_solve_lds_panel<5, 16, K>); break;
-        case 6: launch(&k_chunk_solve_lds_panel<6, 16, K>); break;
-        case 7: launch(&k_chunk_solve_lds_panel<7, 16, K>); break;
-        case 8: launch(&k_chunk_solve_lds_panel<8, 16, K>); break;
-    }
-    MISPEC_HIP(hipGetLastError());
-    return true;
-}
-
-template <int K>
-void solve_level_panel(const mispec_ctx& ctx, const BandLevel& lev, const double* f, int64_t ldf, double* x, int64_t ldx)
-{
-    if (lev.P == 1)
-    {
-        if (lev.inv.p)
             launch_row_gemv_panel(ctx, lev.inv.p, lev.N, lev.N, lev.N, f, ldf, K, x, ldx);
+        }
         else
-            for (int c = 0; c < K; c++)
-                launch_chunk_solve(ctx, lev, dim3(1), f + c * ldf, x + c * ldx);
+            sweep_by_column(x, ldx);
         return;
     }
-    const bool narrow = !lev.cs.wide && lev.b <= 8;
-    double* const y = lev.py.p;
-    double* const g = lev.pg.p;
-    double* const xs = lev.pxs.p;
-    const int64_t ldy = lev.pld, lds = lev.pld_s;
+    const LevelScratch s = level_scratch<K>(lev);
     if (lev.binv.p)
     {
-        hipLaunchKernelGGL(k_block_gemv_panel<K>, dim3(unsigned((lev.binv_ld + 63) / 64), unsigned(lev.P)), dim3(64 * kBlockGemvWaves), 0,
-                           ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.binv_ld, lev.binv.p, f, ldf, y, ldy);
+        hipLaunchKernelGGL(k_block_gemv<K>, dim3(unsigned((lev.binv_ld + 63) / 64), unsigned(lev.P)), dim3(64 * kBlockGemvWaves), 0,
+                           ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.binv_ld, lev.binv.p, f, ldf, s.y, s.ldy);
         MISPEC_HIP(hipGetLastError());
     }
-    else if (K == 4 && kSweepPairsUpTo >= lev.b && launch_chunk_solve_panel<2>(ctx, lev, f, ldf, y, ldy))
-        launch_chunk_solve_panel<2>(ctx, lev, f + 2 * ldf, ldf, y + 2 * ldy, ldy);
-    else if (!launch_chunk_solve_panel<K>(ctx, lev, f, ldf, y, ldy))
-        for (int c = 0; c < K; c++)
-            launch_chunk_solve(ctx, lev, dim3(unsigned((lev.P + kChunkThreads - 1) / kChunkThreads)), f + c * ldf, y + c * ldy);
-    if (narrow)
-    {
-        const dim3 grid(unsigned(((lev.P - 1) * lev.b + kThreads - 1) / kThreads));
-        if (lev.b <= 4)
-            hipLaunchKernelGGL((k_sep_rhs_panel<4, K>), grid, dim3(kThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, ldf, y, ldy,
-                               g, lds);
-        else
-            hipLaunchKernelGGL((k_sep_rhs_panel<8, K>), grid, dim3(kThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, ldf, y, ldy,
-                               g, lds);
-    }
-    else
-        for (int c = 0; c < K; c++)
-            launch_sep_rhs(ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f + c * ldf, y + c * ldy, g + c * lds);
-    MISPEC_HIP(hipGetLastError());
-    solve_level_panel<K>(ctx, *lev.next, g, lds, xs, lds);
-    const int64_t longest = std::max<int64_t>(lev.L, lev.N - (lev.P - 1) * lev.L);
-    const dim3 bgrid(unsigned(lev.P), unsigned((longest + kBackPiece - 1) / kBackPiece));
-    if (narrow)
-        hipLaunchKernelGGL(k_back_subst_panel<K>, bgrid, dim3(kBackThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, y, ldy, xs, lds, x,
-                           ldx);
-    else
-        for (int c = 0; c < K; c++)
-            hipLaunchKernelGGL(k_back_subst, bgrid, dim3(kBackThreads), 0, ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, y + c * ldy, xs + c * lds,
-                               x + c * ldx);
-    MISPEC_HIP(hipGetLastError());
+    else if (K == 4 && kSweepPairsUpTo >= lev.b && launch_chunk_solve_lds<2>(ctx, lev, f, ldf, s.y, s.ldy))
+        launch_chunk_solve_lds<2>(ctx, lev, f + 2 * ldf, ldf, s.y + 2 * s.ldy, s.ldy);
+    else if (K == 1 || !launch_chunk_solve_lds<K>(ctx, lev, f, ldf, s.y, s.ldy))
+        sweep_by_column(s.y, s.ldy);
+    launch_sep_rhs<K>(ctx, lev, f, ldf, s.y, s.ldy, s.g, s.lds);
+    solve_level<K>(ctx, *lev.next, s.g, s.lds, s.xs, s.lds);
+    launch_back_subst<K>(ctx, lev, s.y, s.ldy, s.xs, s.lds, x, ldx);
 }
+void solve_level(const mispec_ctx& ctx, const BandLevel& lev, const double* f, double* x) { solve_level<1>(ctx, lev, f, 0, x, 0); }
 
 // ---- G^{-1} and G^{-T} for the factor G G' = M of a positive definite band (SparseCholesky beyond the dense limit) -------
 // In the nested order (chunk interiors, then separators, recursively) M = G G' with
@@ -2380,9 +2068,8 @@ void chol_forward(const mispec_ctx& ctx, const BandLevel& lev, const double* f, 
         return;
     }
     const int64_t nsep = (lev.P - 1) * lev.b;
-    launch_chunk_solve(ctx, lev, dim3(unsigned((lev.P + kChunkThreads - 1) / kChunkThreads)), f, lev.y.p, 0, u);
-    launch_sep_rhs(ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.band.p, f, lev.y.p, lev.g.p);
-    MISPEC_HIP(hipGetLastError());
+    launch_chunk_solve(ctx, lev, f, lev.y.p, 0, u);
+    launch_sep_rhs<1>(ctx, lev, f, 0, lev.y.p, 0, lev.g.p, 0);
     chol_forward(ctx, *lev.next, lev.g.p, lev.xs.p);
     hipLaunchKernelGGL(k_sep_move, blocks(nsep), dim3(kThreads), 0, ctx.stream, nsep, lev.b, lev.L, lev.xs.p, u, 1);
     MISPEC_HIP(hipGetLastError());
@@ -2400,13 +2087,8 @@ void chol_backward(const mispec_ctx& ctx, const BandLevel& lev, const double* u,
     hipLaunchKernelGGL(k_sep_move, blocks(nsep), dim3(kThreads), 0, ctx.stream, nsep, lev.b, lev.L, u, lev.g.p, 0);
     MISPEC_HIP(hipGetLastError());
     chol_backward(ctx, *lev.next, lev.g.p, lev.xs.p);
-    launch_chunk_solve(ctx, lev, dim3(unsigned((lev.P + kChunkThreads - 1) / kChunkThreads)), u, lev.y.p, 2, nullptr);
-    {
-        const int64_t longest = std::max<int64_t>(lev.L, lev.N - (lev.P - 1) * lev.L);
-        hipLaunchKernelGGL(k_back_subst, dim3(unsigned(lev.P), unsigned((longest + kBackPiece - 1) / kBackPiece)), dim3(kBackThreads), 0,
-                           ctx.stream, lev.N, lev.b, lev.L, lev.P, lev.W.p, lev.y.p, lev.xs.p, x);
-    }
-    MISPEC_HIP(hipGetLastError());
+    launch_chunk_solve(ctx, lev, u, lev.y.p, 2, nullptr);
+    launch_back_subst<1>(ctx, lev, lev.y.p, 0, lev.xs.p, 0, x, 0);
 }
 
 // dense LU with partial pivoting -> explicit inverse (column-major), host
@@ -2477,15 +2159,36 @@ void dense_inverse(int n, std::vector<T>& A, std::vector<T>& inv)
 namespace {
 inline dim3 row_blocks(int64_t n) { return dim3(unsigned((n + kThreads - 1) / kThreads)); }
 
-// y += (A - sigma B)^{-1}_approx (x - (A - sigma B) y): one step of iterative refinement with the factorisation at hand
-void refine_once(const mispec_symshift& S, const double* x_dev, double* y_dev)
+// The vectors of a solve beside the levels' own — residual and correction of a refinement step, right-hand side and solution of a
+// reordered matrix in stored order: the handle's single vectors for K = 1, its panels of leading dimension panel_ld (block_scratch)
+// for K = 2 and 4.
+struct SolveScratch
+{
+    double *r, *dy, *px, *py;
+    int64_t ld;
+};
+template <int K>
+SolveScratch solve_scratch(const mispec_symshift& S)
+{
+    if (K == 1)
+        return {S.ref_r.p, S.ref_dy.p, S.perm_x.p, S.perm_y.p, 0};
+    return {S.panel_r.p, S.panel_dy.p, S.panel_px.p, S.panel_py.p, S.panel_ld};
+}
+
+// y += (A - sigma B)^{-1}_approx (x - (A - sigma B) y): one step of iterative refinement with the factorisation at hand, for K
+// columns (the residual and the update are elementwise kernels, run per column)
+template <int K>
+void refine_once(const mispec_symshift& S, const double* x, int64_t ldx, double* y, int64_t ldy)
 {
     hipStream_t st = S.ctx->stream;
-    hipLaunchKernelGGL(k_band_resid, row_blocks(S.n), dim3(kThreads), 0, st, S.n, S.band_b, S.sigma, S.band0_dev.p,
-                       S.pencil ? S.bandB0_dev.p : nullptr, x_dev, y_dev, S.ref_r.p);
+    const SolveScratch s = solve_scratch<K>(S);
+    for (int c = 0; c < K; c++)
+        hipLaunchKernelGGL(k_band_resid, row_blocks(S.n), dim3(kThreads), 0, st, S.n, S.band_b, S.sigma, S.band0_dev.p,
+                           S.pencil ? S.bandB0_dev.p : nullptr, x + c * ldx, y + c * ldy, s.r + c * s.ld);
     MISPEC_HIP(hipGetLastError());
-    solve_level(*S.ctx, *S.top, S.ref_r.p, S.ref_dy.p);
-    hipLaunchKernelGGL(k_add_inplace, row_blocks(S.n), dim3(kThreads), 0, st, S.n, y_dev, S.ref_dy.p);
+    solve_level<K>(*S.ctx, *S.top, s.r, s.ld, s.dy, s.ld);
+    for (int c = 0; c < K; c++)
+        hipLaunchKernelGGL(k_add_inplace, row_blocks(S.n), dim3(kThreads), 0, st, S.n, y + c * ldy, s.dy + c * s.ld);
     MISPEC_HIP(hipGetLastError());
 }
 
@@ -2580,7 +2283,7 @@ void calibrate_refinement(mispec_symshift& S, const FactorStats& fs)
         }
         prev = omega;
         S.refine_steps = it + 1;
-        refine_once(S, px.p, py.p);
+        refine_once<1>(S, px.p, 0, py.p, 0);
     }
     S.probe_backward_error = omega;
     // The step count was calibrated on ONE probe right-hand side.  With boosted pivots the factors are those of a perturbed
@@ -2627,31 +2330,44 @@ void perm_scratch(const mispec_symshift& S)
         S.perm_y.alloc(size_t(S.n));
     }
 }
+
+// Y[:, c] = (A - sigma B)^{-1} X[:, c] for the K columns of a panel; K = 1 is the single solve
+template <int K>
+void shiftsolve(const mispec_symshift& S, const double* X, int64_t ldx, double* Y, int64_t ldy)
+{
+    if (S.dense)
+    {
+        launch_row_gemv_panel(*S.ctx, S.inverse.p, S.n, S.n, S.n, X, ldx, K, Y, ldy);
+        return;
+    }
+    const double* x = X;
+    double* y = Y;
+    int64_t lx = ldx, ly = ldy;
+    if (S.reordered())  // the caller's index order is kept: x -> stored order (per column), solve with P (A - sigma B) P', y back
+    {
+        if (K == 1)
+            perm_scratch(S);
+        const SolveScratch s = solve_scratch<K>(S);
+        for (int c = 0; c < K; c++)
+            to_stored_order(S, X + c * ldx, s.px + c * s.ld);
+        x = s.px;
+        y = s.py;
+        lx = ly = s.ld;
+    }
+    solve_level<K>(*S.ctx, *S.top, x, lx, y, ly);
+    for (int it = 0; it < S.refine_steps; it++)
+        refine_once<K>(S, x, lx, y, ly);
+    if (S.reordered())
+        for (int c = 0; c < K; c++)
+            from_stored_order(S, y + c * ly, Y + c * ldy);
+}
 }  // namespace
 
 void launch_shiftsolve(const mispec_symshift& S, const double* x_dev, double* y_dev)
 {
     if (!S.factored)
         throw Error(MISPEC_ELOGIC, "SparseSymShiftSolve: need to call set_shift() first");
-    if (S.dense)
-        launch_row_gemv(*S.ctx, S.inverse.p, S.n, S.n, S.n, x_dev, y_dev);
-    else
-    {
-        const double* x = x_dev;
-        double* y = y_dev;
-        if (S.reordered())  // the caller's index order is kept: x -> stored order, solve with P (A - sigma B) P', y back
-        {
-            perm_scratch(S);
-            to_stored_order(S, x_dev, S.perm_x.p);
-            x = S.perm_x.p;
-            y = S.perm_y.p;
-        }
-        solve_level(*S.ctx, *S.top, x, y);
-        for (int it = 0; it < S.refine_steps; it++)
-            refine_once(S, x, y);
-        if (S.reordered())
-            from_stored_order(S, S.perm_y.p, y_dev);
-    }
+    shiftsolve<1>(S, x_dev, 0, y_dev, 0);
 }
 
 // ---- block solve: k right-hand sides, panels of 4 and 2 columns ------------------------------------------------------------
@@ -2659,44 +2375,6 @@ namespace {
 // Panel widths that `auto` uses, widest first: a width stays here only while its panels measured faster than as many single
 // solves on the paths that have panel kernels (tools/bench_shift_block.py).
 constexpr int kAutoWidths[] = {4, 2};
-
-template <int K>
-void shiftsolve_panel(const mispec_symshift& S, const double* X, int64_t ldx, double* Y, int64_t ldy)
-{
-    if (S.dense)
-    {
-        launch_row_gemv_panel(*S.ctx, S.inverse.p, S.n, S.n, S.n, X, ldx, K, Y, ldy);
-        return;
-    }
-    const int64_t pld = S.panel_ld;
-    const double* x = X;
-    double* y = Y;
-    int64_t lx = ldx, ly = ldy;
-    if (S.reordered())  // gather and scatter per column, as the single solve does them
-    {
-        for (int c = 0; c < K; c++)
-            to_stored_order(S, X + c * ldx, S.panel_px.p + c * pld);
-        x = S.panel_px.p;
-        y = S.panel_py.p;
-        lx = ly = pld;
-    }
-    solve_level_panel<K>(*S.ctx, *S.top, x, lx, y, ly);
-    hipStream_t st = S.ctx->stream;
-    for (int it = 0; it < S.refine_steps; it++)  // refine_once for every column: the residual and the update are elementwise kernels
-    {
-        for (int c = 0; c < K; c++)
-            hipLaunchKernelGGL(k_band_resid, row_blocks(S.n), dim3(kThreads), 0, st, S.n, S.band_b, S.sigma, S.band0_dev.p,
-                               S.pencil ? S.bandB0_dev.p : nullptr, x + c * lx, y + c * ly, S.panel_r.p + c * pld);
-        MISPEC_HIP(hipGetLastError());
-        solve_level_panel<K>(*S.ctx, *S.top, S.panel_r.p, pld, S.panel_dy.p, pld);
-        for (int c = 0; c < K; c++)
-            hipLaunchKernelGGL(k_add_inplace, row_blocks(S.n), dim3(kThreads), 0, st, S.n, y + c * ly, S.panel_dy.p + c * pld);
-        MISPEC_HIP(hipGetLastError());
-    }
-    if (S.reordered())
-        for (int c = 0; c < K; c++)
-            from_stored_order(S, S.panel_py.p + c * pld, Y + c * ldy);
-}
 
 // the panel buffers of the handle and of the levels in place now, for the widest panel; nothing is allocated once they exist
 void block_scratch(const mispec_symshift& S)
@@ -2760,11 +2438,11 @@ void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int6
         const double* X = X_dev + int64_t(c) * ldx;
         double* Y = Y_dev + int64_t(c) * ldy;
         if (w == 4)
-            shiftsolve_panel<4>(S, X, ldx, Y, ldy);
+            shiftsolve<4>(S, X, ldx, Y, ldy);
         else if (w == 2)
-            shiftsolve_panel<2>(S, X, ldx, Y, ldy);
+            shiftsolve<2>(S, X, ldx, Y, ldy);
         else
-            launch_shiftsolve(S, X, Y);
+            shiftsolve<1>(S, X, ldx, Y, ldy);
         c += w;
     }
 }

@@ -73,7 +73,8 @@ namespace mispec {
 void launch_shiftsolve(const mispec_symshift& S, const double* x_dev, double* y_dev);
 // Y[:, c] = (A - sigma B)^{-1} X[:, c] for c < k: column-major device blocks with ldx, ldy >= n that do not overlap, enqueued on
 // the context stream.  The columns are cut into panels of 4 and 2 (option shift_block; shiftsolve_block_plan) that share one pass
-// over the factor where a panel kernel exists; every column has exactly the bits launch_shiftsolve gives for it alone.
+// over the factor where a kernel is instantiated for that width; every column has exactly the bits launch_shiftsolve — the same
+// code at width 1 — gives for it alone.
 void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);
 // the cut of k columns: widths 4 / 2 / 1, widest first.  panel: 0 = what option shift_block says, 1 = single columns, 2 | 4 = the
 // widest panel

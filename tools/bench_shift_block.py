@@ -8,6 +8,8 @@ variants alternating in one process; the whole run is repeated (--runs) to show 
   n = 1e6, b = 8             sweep kernels; the second level (band 15) is wide and loops over the columns
   n = 2e5, b = 3             explicit chunk inverses
   n = 4096, b = 16           dense inverse
+  n = 1e6, b = 32            wide band: one wavefront per chunk, every step loops over the columns (the panel variants guard
+                             nothing here; the single solves time the widest separator kernel and the wide back substitution)
 
 One JSON line per (run, shape, k): ms per call and per column of each variant, the ratio to the single solves, and the bytes per
 second on the algorithmic bytes of the TOP level of a panel (factor once + 16 n K; the deeper levels hold 1/32 of the rows):
@@ -27,7 +29,8 @@ import scipy.sparse as sp
 
 import spectra_amd as sa
 
-SHAPES = [(2_000_000, 3, "sweeps"), (1_000_000, 8, "sweeps"), (200_000, 3, "chunk inverses"), (4096, 16, "dense inverse")]
+SHAPES = [(2_000_000, 3, "sweeps"), (1_000_000, 8, "sweeps"), (200_000, 3, "chunk inverses"), (4096, 16, "dense inverse"),
+          (1_000_000, 32, "wide band")]
 COLUMNS = (2, 4, 8, 21)
 
 
