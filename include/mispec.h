@@ -345,7 +345,12 @@ int mispec_spmm_time(const mispec_csr* A, const double* X_dev, int64_t ldx, int 
  * wide AS IT COMES is reordered at construction (reverse Cuthill-McKee on the pattern, as the reference's sparse factorisations
  * order theirs) and takes the banded path when the reordered half-bandwidth is <= 64 — a banded matrix in a scattering row
  * order, path- / ladder-like graphs; solves and eigenvectors keep the caller's index order (mispec_symshift_bandwidth reports both
- * widths; MISPEC_REORDER=none opts out).  Other sparsity patterns are rejected by set_shift (MISPEC_EINVAL).
+ * widths; MISPEC_REORDER=none opts out).  Beyond n = 4096 a band of half-bandwidth 65 ... 512 (as given, or after that ordering
+ * when it is narrower) takes the block-tridiagonal path: A - sigma B cut into dense s x s blocks, s = the half-bandwidth, block
+ * LU without pivoting across blocks — S_0 = D_0, L_i = E_i S_{i-1}^{-1}, S_i = D_i - L_i E_i' — with S_i^{-1} and L_i kept in HBM
+ * (16 n s bytes) and the same calibrated refinement for interior shifts (mispec_symshift_path, mispec_symshift_path_info).
+ * Other sparsity patterns — a band wider than 512 after the ordering: a general sparse factorisation is not provided — are
+ * rejected by set_shift (MISPEC_EINVAL).
  * Input: one triangle of a compressed matrix, as for mispec_csr_from_triangle.
  * ------------------------------------------------------------------------- */
 typedef struct mispec_symshift mispec_symshift;
@@ -353,7 +358,8 @@ int mispec_symshift_create(mispec_ctx* ctx, int64_t n, const int32_t* outer_host
                            const double* val_host, char uplo, int row_major, mispec_symshift** out);
 /* Pencil form — SymShiftInvert<double, Eigen::Sparse, Eigen::Sparse> (MatOp/SymShiftInvert.h:140-208): the operator
  * (A - sigma B)^{-1} for two sparse symmetric matrices given by one triangle each; same restrictions as above on
- * the pattern of A - sigma B (banded with half-bandwidth <= 64, or n <= 4096). */
+ * the pattern of A - sigma B (banded with half-bandwidth <= 64 for the chunk kernels or <= 512 for the block-tridiagonal path, or
+ * n <= 4096). */
 int mispec_symshift_create_pencil(mispec_ctx* ctx, int64_t n, const int32_t* a_outer, const int32_t* a_inner,
                                   const double* a_val, char a_uplo, int a_row_major, const int32_t* b_outer,
                                   const int32_t* b_inner, const double* b_val, char b_uplo, int b_row_major,
@@ -368,9 +374,19 @@ int64_t mispec_symshift_rows(const mispec_symshift* S);
 int mispec_symshift_bandwidth(const mispec_symshift* S, int64_t* as_given, int64_t* stored, int* reordered);
 /* The levels the banded path plans for an n x n matrix of this half-bandwidth (host arithmetic only): per level rows, half-bandwidth
  * (2b - 1 of the level above), chunk length, chunk count; the last level (one chunk) is the dense one.  Returns the number of
- * levels (arrays hold up to max_levels entries, may be NULL), 0 when the dense path is taken, MISPEC_EINVAL when unsupported. */
+ * levels (arrays hold up to max_levels entries, may be NULL), 0 when the dense path is taken, MISPEC_EINVAL when unsupported.
+ * This describes the chunk path only: a band that takes the block-tridiagonal path (mispec_symshift_path == 2) has no levels
+ * and is MISPEC_EINVAL here. */
 int mispec_symshift_level_plan(int64_t n, int64_t half_bandwidth, int max_levels, int64_t* rows, int64_t* bandwidth,
                                int64_t* chunk_rows, int64_t* chunks);
+/* The path an n x n symmetric operator of this half-bandwidth takes (host arithmetic only, no device): 0 = the explicit inverse
+ * (n <= 4096), 1 = the partitioned chunk path (half-bandwidth <= 8, or <= 64 beyond n = 4096), 2 = the block-tridiagonal path
+ * (half-bandwidth 65 ... 512 beyond n = 4096); MISPEC_EINVAL when unsupported or for n < 1 or half_bandwidth < 0. */
+int mispec_symshift_path(int64_t n, int64_t half_bandwidth);
+/* The path of this operator (valid after construction) and, on path 2, the block layout: rows per block s, number of blocks
+ * ceil(n / s), bytes of the factor kept in HBM after set_shift (16 blocks s^2); zeros on paths 0 and 1.  path is -1 for an operator
+ * that set_shift will refuse.  Any output pointer may be NULL. */
+int mispec_symshift_path_info(const mispec_symshift* S, int* path, int64_t* block_rows, int64_t* blocks, int64_t* factor_bytes);
 /* set_shift(sigma) (SparseSymShiftSolve.h:85-95): MISPEC_EINVAL "factorization failed with the given shift" on breakdown */
 int mispec_symshift_set_shift(mispec_symshift* S, double sigma);
 int mispec_symshift_solve(const mispec_symshift* S, const double* x_dev, double* y_dev);        /* device pointers */
@@ -385,7 +401,8 @@ int mispec_symshift_solve_host(const mispec_symshift* S, const double* x_host, d
  * 2 | 4 cap the width, 0 allows none), each of which reads the factor once where a panel kernel exists: the narrow-band
  * partitioned levels (half-bandwidth <= 8: sweeps, explicit chunk inverses, separator right-hand sides, back substitution) and the
  * dense inverses (n <= 4096, last level).  Wide levels (half-bandwidth 9 ... 64) and remaining single columns run the single
- * kernels per column.  Every column has exactly the bits mispec_symshift_solve gives for it alone, on every path (pencils,
+ * kernels per column; the block-tridiagonal path runs every column on its own whatever shift_block says.  Every column has
+ * exactly the bits mispec_symshift_solve gives for it alone, on every path (pencils,
  * reordered matrices, general operators, indefinite shifts with their refinement steps).
  * MISPEC_EINVAL: NULL pointer, k < 1, ldx < n or ldy < n; MISPEC_ELOGIC: set_shift has not been called. */
 int mispec_symshift_solve_block(const mispec_symshift* S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);

@@ -274,6 +274,13 @@ class _ShiftBlock:
         """Y[:, :k] = (A - sigma B)^{-1} X[:, :k] on device pointers (column-major, ldx, ldy >= n), enqueued on the context's stream."""
         check(lib().mispec_symshift_solve_block(self.h, C.c_void_p(int(x_ptr)), int(ldx), int(k), C.c_void_p(int(y_ptr)), int(ldy)))
 
+    def path_info(self):
+        """{path, block_rows, blocks, factor_bytes} (mispec_symshift_path_info): path 0 = explicit inverse, 1 = chunk path, 2 = the
+        block-tridiagonal path with its block layout and the bytes of its factor (zeros on the other paths), -1 = unsupported."""
+        p, s, nb, fb = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().mispec_symshift_path_info(self.h, C.byref(p), C.byref(s), C.byref(nb), C.byref(fb)))
+        return {"path": p.value, "block_rows": s.value, "blocks": nb.value, "factor_bytes": fb.value}
+
 
 def dia_sym_plan(offsets, reach=-1):
     """The rule of option `dia_sym` (mispec_dia_sym_plan; host only): for the diagonal offsets given, (flags, lead_blocks) —

@@ -111,6 +111,8 @@ SIGNATURES = {
     "mispec_spmm_time": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, C.c_int64, C.c_int, C.POINTER(C.c_float)]),
     "mispec_spmm_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "mispec_symshift_level_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _lp, _lp, _lp, _lp]),
+    "mispec_symshift_path": (C.c_int, [C.c_int64, C.c_int64]),
+    "mispec_symshift_path_info": (C.c_int, [_vp, C.POINTER(C.c_int), _lp, _lp, _lp]),
     "mispec_symshift_create": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_char, C.c_int, _vpp]),
     "mispec_symshift_destroy": (C.c_int, [_vp]),
     "mispec_symshift_rows": (C.c_int64, [_vp]),

@@ -2175,6 +2175,20 @@ SolveScratch solve_scratch(const mispec_symshift& S)
     return {S.panel_r.p, S.panel_dy.p, S.panel_px.p, S.panel_py.p, S.panel_ld};
 }
 
+// "The factorisation's solve" of the handle, in stored order: the levels of the chunk path, or the block-tridiagonal chain — which
+// has single-column kernels only and is never asked for a panel (launch_shiftsolve_block).
+template <int K>
+void factor_solve(const mispec_symshift& S, const double* f, int64_t ldf, double* x, int64_t ldx)
+{
+    if (S.blocktri)
+    {
+        for (int c = 0; c < K; c++)
+            blocktri_solve(S, f + c * ldf, x + c * ldx);
+        return;
+    }
+    solve_level<K>(*S.ctx, *S.top, f, ldf, x, ldx);
+}
+
 // y += (A - sigma B)^{-1}_approx (x - (A - sigma B) y): one step of iterative refinement with the factorisation at hand, for K
 // columns (the residual and the update are elementwise kernels, run per column)
 template <int K>
@@ -2186,7 +2200,7 @@ void refine_once(const mispec_symshift& S, const double* x, int64_t ldx, double*
         hipLaunchKernelGGL(k_band_resid, row_blocks(S.n), dim3(kThreads), 0, st, S.n, S.band_b, S.sigma, S.band0_dev.p,
                            S.pencil ? S.bandB0_dev.p : nullptr, x + c * ldx, y + c * ldy, s.r + c * s.ld);
     MISPEC_HIP(hipGetLastError());
-    solve_level<K>(*S.ctx, *S.top, s.r, s.ld, s.dy, s.ld);
+    factor_solve<K>(S, s.r, s.ld, s.dy, s.ld);
     for (int c = 0; c < K; c++)
         hipLaunchKernelGGL(k_add_inplace, row_blocks(S.n), dim3(kThreads), 0, st, S.n, y + c * ldy, s.dy + c * s.ld);
     MISPEC_HIP(hipGetLastError());
@@ -2244,7 +2258,7 @@ void calibrate_refinement(mispec_symshift& S, const FactorStats& fs)
     norms.alloc(3);
     hipLaunchKernelGGL(k_probe_fill, row_blocks(n), dim3(kThreads), 0, st, n, px.p);
     MISPEC_HIP(hipGetLastError());
-    solve_level(*S.ctx, *S.top, px.p, py.p);
+    factor_solve<1>(S, px.p, 0, py.p, 0);
     const unsigned grid = unsigned(std::min<int64_t>((n + kThreads - 1) / kThreads, 1024));
     constexpr int kMaxRefine = 12;
     constexpr double kTarget = 4.0e-15;  // a few eps: what a backward-stable solve of a band matrix gives
@@ -2354,7 +2368,7 @@ void shiftsolve(const mispec_symshift& S, const double* X, int64_t ldx, double* 
         y = s.py;
         lx = ly = s.ld;
     }
-    solve_level<K>(*S.ctx, *S.top, x, lx, y, ly);
+    factor_solve<K>(S, x, lx, y, ly);
     for (int it = 0; it < S.refine_steps; it++)
         refine_once<K>(S, x, lx, y, ly);
     if (S.reordered())
@@ -2429,7 +2443,8 @@ void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int6
     MISPEC_REQUIRE(ldx >= S.n && ldy >= S.n, "mispec_symshift_solve_block: leading dimension too small");
     if (!S.factored)
         throw Error(MISPEC_ELOGIC, "SparseSymShiftSolve: need to call set_shift() first");
-    const std::vector<int> widths = shiftsolve_block_plan(k, 0);
+    // the block-tridiagonal path has no panel kernels: the column loop whatever shift_block says
+    const std::vector<int> widths = S.blocktri ? std::vector<int>(size_t(k), 1) : shiftsolve_block_plan(k, 0);
     if (widths[0] > 1)
         block_scratch(S);
     int c = 0;
@@ -2537,7 +2552,8 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
         {
             // Too wide for the band kernels as it comes and too large for the dense path: try a bandwidth-reducing ordering
             // (reverse Cuthill-McKee on the pattern of A (+ B)) before giving up — the reference's SparseLU / SimplicialLDLT
-            // order their matrix too.  Adopted only if the reordered band fits the kernels.
+            // order their matrix too.  Adopted if the reordered band fits the chunk kernels; else the narrower of the two bands —
+            // as given, reordered — goes to the block-tridiagonal path if it fits that (the ordering kept only when it is narrower).
             std::vector<int32_t> rp(size_t(n) + 1, 0);
             const auto count = [&](int64_t r, int64_t c, double) {
                 if (r != c)
@@ -2575,7 +2591,7 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
                 for_each_entry(A, n, width);
                 if (B)
                     for_each_entry(*B, n, width);
-                if (band_path(n, hb))
+                if (band_path(n, hb) || (hb < S->half_bandwidth && hb <= kMaxBlockBandwidth))
                 {
                     S->half_bandwidth = hb;
                     S->perm_host = perm;
@@ -2584,7 +2600,8 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
                     inv.clear();
             }
         }
-        if (band_path(n, S->half_bandwidth))
+        const ShiftPath path = shift_path(n, S->half_bandwidth);
+        if (path == ShiftPath::chunk || path == ShiftPath::blocktri)
         {
             // ... then, for a band, the band itself (assembled once; every set_shift() starts from it)
             S->band_b = int(std::max<int64_t>(1, std::min<int64_t>(S->half_bandwidth, n - 1)));  // a diagonal matrix: width 1, zeros
@@ -2612,7 +2629,7 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
                 S->perm_dev.alloc(size_t(n));
                 MISPEC_HIP(hipMemcpy(S->perm_dev.p, S->perm_host.data(), size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice));
             }
-            if (factored_on_device(n, S->band_b))
+            if (path == ShiftPath::blocktri || factored_on_device(n, S->band_b))
             {
                 ctx->make_current();
                 S->band0_dev.alloc(S->band0.size());
@@ -2734,6 +2751,37 @@ extern "C" int mispec_symshift_bandwidth(const mispec_symshift* S, int64_t* as_g
     });
 }
 
+extern "C" int mispec_symshift_path(int64_t n, int64_t half_bandwidth)
+{
+    int path = 0;
+    const int rc = guarded([&] {
+        MISPEC_REQUIRE(n >= 1 && half_bandwidth >= 0, "mispec_symshift_path: bad argument");
+        const ShiftPath p = shift_path(n, half_bandwidth);
+        MISPEC_REQUIRE(p != ShiftPath::unsupported,
+                       "SparseSymShiftSolve: only banded matrices (half-bandwidth <= 64 for the chunk kernels, <= 512 for the "
+                       "block-tridiagonal path) or n <= 4096 are supported on the GPU");
+        path = int(p);
+    });
+    return rc == MISPEC_OK ? path : rc;
+}
+
+extern "C" int mispec_symshift_path_info(const mispec_symshift* S, int* path, int64_t* block_rows, int64_t* blocks, int64_t* factor_bytes)
+{
+    return guarded([&] {
+        MISPEC_REQUIRE(S, "mispec_symshift_path_info: NULL argument");
+        const ShiftPath p = S->path();
+        const int64_t s = p == ShiftPath::blocktri ? S->band_b : 0, N = s ? (S->n + s - 1) / s : 0;
+        if (path)
+            *path = int(p);
+        if (block_rows)
+            *block_rows = s;
+        if (blocks)
+            *blocks = N;
+        if (factor_bytes)
+            *factor_bytes = 16 * N * s * s;
+    });
+}
+
 // The levels the banded path plans for an n x n matrix of the given half-bandwidth (no device needed): rows, half-bandwidth,
 // chunk length and chunk count per level, the last level (one chunk) being the dense one.  Returns the number of levels, 0 when
 // the matrix takes the dense path instead (n <= 4096, band wider than 8), MISPEC_EINVAL when it is unsupported.
@@ -2790,8 +2838,26 @@ extern "C" int mispec_symshift_set_shift(mispec_symshift* S, double sigma)
         S->ctx->make_current();
         S->factored = false;
         S->sigma = sigma;
-        const int64_t n = S->n, b = S->half_bandwidth;
-        if (!S->general && band_path(n, b))
+        const int64_t n = S->n;
+        const ShiftPath path = S->path();
+        if (path == ShiftPath::blocktri)
+        {
+            // the whole chain is enqueued and its record read once (shift_blocktri.hip); interior shifts get the chunk path's
+            // calibrated refinement with this factorisation's solve
+            MISPEC_REQUIRE(!S->want_cholesky, "internal: SparseCholesky never takes the block-tridiagonal path");
+            S->dense = false;
+            S->top.reset();
+            FactorStats fs;
+            {
+                PhaseTimer pt("blocktri_factor (all blocks)", n, int(S->band_b));
+                fs.min_pivot_ratio = blocktri_factor(*S, sigma);
+            }
+            {
+                PhaseTimer pt("calibrate_refinement", n, int(S->band_b));
+                calibrate_refinement(*S, fs);
+            }
+        }
+        else if (path == ShiftPath::chunk)
         {
             struct WideTop  // the planning mode of this factorisation, whichever way the scope is left
             {
@@ -2881,7 +2947,7 @@ extern "C" int mispec_symshift_set_shift(mispec_symshift* S, double sigma)
                 }
             }
         }
-        else if (n <= kMaxDense)
+        else if (path == ShiftPath::inverse)
         {
             std::vector<double> A(size_t(n) * n, 0.0), inv;
             for (size_t e = 0; e < S->vals.size(); e++)
@@ -2906,8 +2972,9 @@ extern "C" int mispec_symshift_set_shift(mispec_symshift* S, double sigma)
         }
         else
             throw Error(MISPEC_EINVAL,
-                        "SparseSymShiftSolve: only banded matrices (half-bandwidth <= 64 as given or after a reverse Cuthill-McKee "
-                        "ordering) or n <= 4096 are supported on the GPU (the reference uses a general sparse LU)");
+                        "SparseSymShiftSolve: only banded matrices (half-bandwidth <= 64 for the chunk kernels, <= 512 for the "
+                        "block-tridiagonal path, as given or after a reverse Cuthill-McKee ordering) or n <= 4096 are supported on the "
+                        "GPU (the reference uses a general sparse LU)");
         S->factored = true;
     });
 }

@@ -12,6 +12,30 @@ constexpr int64_t kMaxDense = 4096;      // dense path: matrix dimension
 // Which path a symmetric operator of dimension n and half-bandwidth b takes: the partitioned band factorisation for narrow bands
 // (any n) and for bands of up to 64 beyond the dense limit; the dense inverse otherwise (n <= kMaxDense), else unsupported.
 inline bool band_path(int64_t n, int64_t b) { return b <= kNarrowBandwidth || (b <= kMaxBandwidth && n > kMaxDense); }
+constexpr int64_t kMaxBlockBandwidth = 512;  // block-tridiagonal path: one s x s block (s = half-bandwidth) is 2 MiB of an XCD's 4 MiB L2
+// The path of (n, b), for every site that decides one: the chunk path where band_path says so, else the explicit inverse up to
+// kMaxDense, else the block-tridiagonal factorisation (shift_blocktri.hip) up to kMaxBlockBandwidth, else none.  The values are
+// those of mispec_symshift_path.
+enum class ShiftPath { unsupported = -1, inverse = 0, chunk = 1, blocktri = 2 };
+inline ShiftPath shift_path(int64_t n, int64_t b)
+{
+    if (band_path(n, b))
+        return ShiftPath::chunk;
+    if (n <= kMaxDense)
+        return ShiftPath::inverse;
+    return b <= kMaxBlockBandwidth ? ShiftPath::blocktri : ShiftPath::unsupported;
+}
+// Block-tridiagonal factor of A - sigma B (shift_blocktri.hip): N = ceil(n / s) blocks of s = band_b rows, the last one padded
+// with identity rows.  S_0 = D_0, L_i = E_i S_{i-1}^{-1}, S_i = D_i - L_i E_i'; kept are S_i^{-1} and L_i, s x s row-major each.
+struct BlockTri
+{
+    int64_t s = 0, N = 0;
+    DevBuf<double> sinv, l;  // N s^2 doubles each (l: block 0 unused)
+    DevBuf<double> w;        // s^2: L_i while S_i is formed from E_i, which lies in l's slot until then
+    DevBuf<double> y, z;     // N s: the padded vectors of a solve
+    DevBuf<unsigned long long> record;  // [0] zero pivot columns, [1] bits of the smallest |pivot| / max |S_i|
+    size_t factor_bytes() const { return 2 * size_t(N) * size_t(s) * size_t(s) * sizeof(double); }
+};
 }  // namespace mispec
 
 struct mispec_symshift
@@ -40,6 +64,13 @@ struct mispec_symshift
     bool factored = false;
     bool dense = false;
     std::unique_ptr<mispec::BandLevel> top;  // banded path
+    std::unique_ptr<mispec::BlockTri> blocktri;  // block-tridiagonal path (65 <= band_b <= 512 beyond the dense limit)
+    mispec::ShiftPath path() const  // a general (non-symmetric) operator has the explicit inverse only
+    {
+        if (general)
+            return n <= mispec::kMaxDense ? mispec::ShiftPath::inverse : mispec::ShiftPath::unsupported;
+        return mispec::shift_path(n, half_bandwidth);
+    }
     mispec::DevBuf<double> inverse;          // dense path: (A - sigma I)^{-1}, n x n column-major
     mutable mispec::DevBuf<double> stage_x, stage_y;
     // Robustness for indefinite A - sigma I (banded path): what the last factorisation saw and the number of iterative
@@ -76,6 +107,13 @@ void launch_shiftsolve(const mispec_symshift& S, const double* x_dev, double* y_
 // over the factor where a kernel is instantiated for that width; every column has exactly the bits launch_shiftsolve — the same
 // code at width 1 — gives for it alone.
 void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int64_t ldx, int k, double* Y_dev, int64_t ldy);
+// Block-tridiagonal path (shift_blocktri.hip).  Factor: assembles the blocks of A - sigma B from the handle's resident band(s) and
+// enqueues the whole chain on the context stream without a host synchronisation, then reads the device record once — throws
+// "factorization failed with the given shift" for an exactly zero pivot column, returns the smallest pivot ratio.  Refuses with
+// MISPEC_ERUNTIME "out of memory" before allocating when the factor does not fit the free device memory.
+double blocktri_factor(mispec_symshift& S, double sigma);
+// y = M^{-1} x in stored order with that factor: device pointers of n doubles, 2 N + 1 launches on the context stream
+void blocktri_solve(const mispec_symshift& S, const double* x_dev, double* y_dev);
 // the cut of k columns: widths 4 / 2 / 1, widest first.  panel: 0 = what option shift_block says, 1 = single columns, 2 | 4 = the
 // widest panel
 std::vector<int> shiftsolve_block_plan(int k, int panel);
