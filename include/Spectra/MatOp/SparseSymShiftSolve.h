@@ -7,8 +7,12 @@
 // LDL' when the half-bandwidth of A — as given, or after the reverse Cuthill-McKee ordering the constructor tries for wider
 // patterns — is <= 8 (any n) or <= 64 with n > 4096, a block-tridiagonal factorisation with dense blocks when it is 65 ... 512 with
 // n > 4096 (csrc/shift_blocktri.hip; 16 n b bytes of factor in HBM), or a dense inverse when n <= 4096 (csrc/shiftsolve.hpp
-// shift_path).  Other patterns — a band wider than 512 after the ordering — throw std::invalid_argument at set_shift().  The solver binds the device operator directly; perform_op() keeps the
-// reference's host-pointer contract for everybody else.
+// shift_path).  Other patterns — a band wider than 512 after the ordering — throw std::invalid_argument at set_shift(), unless the
+// operator was constructed with ShiftSolver::Auto or ShiftSolver::Iterative (or option shift_solver says so): it then applies
+// (A - sigma I)^{-1} by Jacobi-preconditioned MINRES on the SpMV's own operator (csrc/shift_minres.hip), every solve to a backward
+// error of 4e-15; set_shift() refuses a shift whose probe solve does not converge, perform_op() throws std::runtime_error for a solve
+// that does not.  The solver binds the device operator directly; perform_op() keeps the reference's host-pointer contract for
+// everybody else.
 #ifndef MISPEC_SPECTRA_SPARSE_SYM_SHIFT_SOLVE_H
 #define MISPEC_SPECTRA_SPARSE_SYM_SHIFT_SOLVE_H
 
@@ -30,7 +34,7 @@ private:
     internal::CtxPtr m_ctx;
     std::shared_ptr<mispec_symshift> m_solver;
 
-    void ingest(const SparseView<Scalar, StorageIndex>& A)
+    void ingest(const SparseView<Scalar, StorageIndex>& A, ShiftSolver solver)
     {
         if (A.rows != A.cols)
             throw std::invalid_argument("SparseSymShiftSolve: matrix must be square");
@@ -40,21 +44,23 @@ private:
         mispec_symshift* raw = nullptr;
         const std::size_t nnz = static_cast<std::size_t>(A.outer[A.rows]);
         const internal::Int32Indices<StorageIndex> outer(A.outer, static_cast<std::size_t>(A.rows) + 1), inner(A.inner, nnz);
-        internal::check(mispec_symshift_create(m_ctx.get(), A.rows, outer.data(), inner.data(), A.values, Uplo == Lower ? 'L' : 'U',
-                                               A.row_major ? 1 : 0, &raw));
+        internal::check(mispec_symshift_create_solver(m_ctx.get(), A.rows, outer.data(), inner.data(), A.values, Uplo == Lower ? 'L' : 'U',
+                                                      A.row_major ? 1 : 0, static_cast<int>(solver), &raw));
         m_solver = std::shared_ptr<mispec_symshift>(raw, [](mispec_symshift* p) { (void) mispec_symshift_destroy(p); });
     }
 
 public:
-    explicit SparseSymShiftSolve(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx = internal::CtxPtr()) :
+    explicit SparseSymShiftSolve(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx = internal::CtxPtr(),
+                                 ShiftSolver solver = ShiftSolver::Default) :
         m_ctx(ctx ? ctx : internal::default_context())
     {
-        ingest(mat);
+        ingest(mat, solver);
     }
 
 #ifdef MISPEC_HAVE_EIGEN
     template <typename Derived>
-    SparseSymShiftSolve(const Eigen::SparseMatrixBase<Derived>& mat) : m_ctx(internal::default_context())
+    SparseSymShiftSolve(const Eigen::SparseMatrixBase<Derived>& mat, ShiftSolver solver = ShiftSolver::Default) :
+        m_ctx(internal::default_context())
     {
         using Plain = Eigen::SparseMatrix<Scalar, Flags, StorageIndex>;
         static_assert(static_cast<int>(Derived::PlainObject::IsRowMajor) == static_cast<int>(Plain::IsRowMajor),
@@ -68,7 +74,7 @@ public:
         v.inner = tmp.innerIndexPtr();
         v.values = tmp.valuePtr();
         v.row_major = Plain::IsRowMajor;
-        ingest(v);
+        ingest(v, solver);
     }
 #endif
 

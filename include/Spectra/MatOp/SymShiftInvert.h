@@ -3,7 +3,8 @@
 // a dense Bunch-Kaufman LDLT depending on the storage of A and B).  Here both matrices are sparse and the
 // factorisation is the device one of SparseSymShiftSolve (spectra_amd/csrc/shiftsolve.hip): banded A - sigma B with
 // half-bandwidth <= 8 (beyond n = 4096: <= 64 on the partitioned path, 65 ... 512 on the block-tridiagonal path), or any pattern
-// with n <= 4096.
+// with n <= 4096.  Constructed with ShiftSolver::Auto or ShiftSolver::Iterative (or under option shift_solver), any other pattern
+// is solved by Jacobi-preconditioned MINRES on the SpMV's own operators of A and B (csrc/shift_minres.hip) — see SparseSymShiftSolve.h.
 #ifndef MISPEC_SPECTRA_SYM_SHIFT_INVERT_H
 #define MISPEC_SPECTRA_SYM_SHIFT_INVERT_H
 
@@ -43,7 +44,7 @@ private:
     internal::CtxPtr m_ctx;
     std::shared_ptr<mispec_symshift> m_solver;
 
-    void ingest(const SparseView<Scalar, int>& A, const SparseView<Scalar, int>& B)
+    void ingest(const SparseView<Scalar, int>& A, const SparseView<Scalar, int>& B, ShiftSolver solver)
     {
         if (A.rows != A.cols || B.rows != A.rows || B.cols != A.rows)
             throw std::invalid_argument("SymShiftInvert: A and B must be square matrices of the same size");
@@ -51,22 +52,24 @@ private:
             throw std::invalid_argument(
                 "SymShiftInvert: the \"FlagsA\" / \"FlagsB\" template parameter does not match the input matrix (ColMajor/RowMajor)");
         mispec_symshift* raw = nullptr;
-        internal::check(mispec_symshift_create_pencil(m_ctx.get(), A.rows, A.outer, A.inner, A.values, UploA == Lower ? 'L' : 'U',
-                                                      A.row_major ? 1 : 0, B.outer, B.inner, B.values, UploB == Lower ? 'L' : 'U',
-                                                      B.row_major ? 1 : 0, &raw));
+        internal::check(mispec_symshift_create_pencil_solver(m_ctx.get(), A.rows, A.outer, A.inner, A.values, UploA == Lower ? 'L' : 'U',
+                                                             A.row_major ? 1 : 0, B.outer, B.inner, B.values, UploB == Lower ? 'L' : 'U',
+                                                             B.row_major ? 1 : 0, static_cast<int>(solver), &raw));
         m_solver = std::shared_ptr<mispec_symshift>(raw, [](mispec_symshift* p) { (void) mispec_symshift_destroy(p); });
     }
 
 public:
-    SymShiftInvert(const SparseView<Scalar, int>& A, const SparseView<Scalar, int>& B, internal::CtxPtr ctx = internal::CtxPtr()) :
+    SymShiftInvert(const SparseView<Scalar, int>& A, const SparseView<Scalar, int>& B, internal::CtxPtr ctx = internal::CtxPtr(),
+                   ShiftSolver solver = ShiftSolver::Default) :
         m_ctx(ctx ? ctx : internal::default_context())
     {
-        ingest(A, B);
+        ingest(A, B, solver);
     }
 
 #ifdef MISPEC_HAVE_EIGEN
     template <typename DerivedA, typename DerivedB>
-    SymShiftInvert(const Eigen::SparseMatrixBase<DerivedA>& A, const Eigen::SparseMatrixBase<DerivedB>& B) :
+    SymShiftInvert(const Eigen::SparseMatrixBase<DerivedA>& A, const Eigen::SparseMatrixBase<DerivedB>& B,
+                   ShiftSolver solver = ShiftSolver::Default) :
         m_ctx(internal::default_context())
     {
         Eigen::SparseMatrix<Scalar, FlagsA, int> a(A);
@@ -78,7 +81,7 @@ public:
         va.row_major = (FlagsA == RowMajor);
         vb.rows = b.rows(), vb.cols = b.cols(), vb.outer = b.outerIndexPtr(), vb.inner = b.innerIndexPtr(), vb.values = b.valuePtr();
         vb.row_major = (FlagsB == RowMajor);
-        ingest(va, vb);
+        ingest(va, vb, solver);
     }
 #endif
 

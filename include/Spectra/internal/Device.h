@@ -11,6 +11,19 @@
 #include "../../mispec.h"
 
 namespace Spectra {
+
+// Which paths a shift-and-invert operator (SparseSymShiftSolve, SymShiftInvert) may take — the solver kinds of
+// mispec_symshift_create_solver: Default = what option shift_solver says (direct unless set), Direct = the factorisations only,
+// Auto = a factorisation where construction finds one, else the iterative path (preconditioned MINRES, any sparsity pattern),
+// Iterative = the iterative path always.
+enum class ShiftSolver
+{
+    Default = -1,
+    Direct = 0,
+    Auto = 1,
+    Iterative = 2
+};
+
 namespace internal {
 
 // MISPEC_EINVAL -> std::invalid_argument (HermEigsBase.h:267-271, Arnoldi.h:148,209),

@@ -76,9 +76,14 @@ const char* mispec_version(void);
  *   shift_block     auto (default) | 0 | 2 | 4                           block shift solve (mispec_symshift_solve_block): the widest panel of
  *                                                                        columns that shares one pass over the factor (0: one solve per
  *                                                                        column; same bits)
+ *   shift_solver    direct (default) | auto | iterative                  shift-and-invert operators constructed afterwards: the direct paths
+ *                                                                        only (every refusal included) | a direct path where construction
+ *                                                                        finds one, else the iterative path (preconditioned MINRES, any
+ *                                                                        pattern) | the iterative path always
  *   shift           comma list of lds=0|1, batch=8|16|32, lanes=8|16|32|64, block_inverse=<MiB>, factor=host|device, wave=0|1,
- *                   profile=0|1, each key at most once — banded shift solve: kernel variants that must agree (tests), set_shift's
- *                   phases on stderr
+ *                   profile=0|1, minres_check=1...64, each key at most once — banded shift solve: kernel variants that must agree
+ *                   (tests), set_shift's phases on stderr; iterative path: iterations enqueued between two reads of the stop flag
+ *                   (default 16; same bits for every value)
  * mispec_get_option returns the value in effect (the one set, else the environment's; not checked), NULL when there is none or
  * the name is unknown, in a buffer of the calling thread that stays valid until that thread calls mispec_get_option again.
  * The reference has no counterpart (its only switches are template parameters). */
@@ -350,7 +355,7 @@ int mispec_spmm_time(const mispec_csr* A, const double* X_dev, int64_t ldx, int 
  * LU without pivoting across blocks — S_0 = D_0, L_i = E_i S_{i-1}^{-1}, S_i = D_i - L_i E_i' — with S_i^{-1} and L_i kept in HBM
  * (16 n s bytes) and the same calibrated refinement for interior shifts (mispec_symshift_path, mispec_symshift_path_info).
  * Other sparsity patterns — a band wider than 512 after the ordering: a general sparse factorisation is not provided — are
- * rejected by set_shift (MISPEC_EINVAL).
+ * rejected by set_shift (MISPEC_EINVAL) unless the operator may take the iterative path (below).
  * Input: one triangle of a compressed matrix, as for mispec_csr_from_triangle.
  * ------------------------------------------------------------------------- */
 typedef struct mispec_symshift mispec_symshift;
@@ -364,6 +369,33 @@ int mispec_symshift_create_pencil(mispec_ctx* ctx, int64_t n, const int32_t* a_o
                                   const double* a_val, char a_uplo, int a_row_major, const int32_t* b_outer,
                                   const int32_t* b_inner, const double* b_val, char b_uplo, int b_row_major,
                                   mispec_symshift** out);
+/* The two constructors above with the solver kind of this operator: -1 = what option shift_solver says (what the constructors
+ * above pass), 0 = direct, 1 = auto, 2 = iterative.  The ITERATIVE PATH (path 3) applies (A - sigma B)^{-1} by MINRES with the
+ * Jacobi preconditioner 1 / |diag(A - sigma B)| on the SpMV's own operators of A and B, for any sparsity pattern and any n >= 1,
+ * definite and indefinite shifts alike: set_shift does O(n) work and solves a probe right-hand side; every solve iterates until
+ * the backward error |x - M y|_inf / (|M|_inf |y|_inf + |x|_inf), from an explicit residual, is <= tol (default 4e-15; up to 3
+ * restarts on the residual; stagnation accepted at <= 1e-13).  A shift whose probe does not get there is refused by set_shift
+ * (MISPEC_EINVAL "... did not converge in N iterations (backward error ...)"; the handle recovers at the next set_shift), a
+ * solve that does not is MISPEC_ERUNTIME with the same wording.  No factor is kept: 11 (pencil: 12) work vectors of n doubles.
+ * The eigensolvers take their steps host-driven on such an operator; as a preconditioner of the block solver of
+ * mispec_extras.h it is refused. */
+int mispec_symshift_create_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
+                                  const double* val_host, char uplo, int row_major, int solver, mispec_symshift** out);
+int mispec_symshift_create_pencil_solver(mispec_ctx* ctx, int64_t n, const int32_t* a_outer, const int32_t* a_inner,
+                                         const double* a_val, char a_uplo, int a_row_major, const int32_t* b_outer,
+                                         const int32_t* b_inner, const double* b_val, char b_uplo, int b_row_major, int solver,
+                                         mispec_symshift** out);
+/* The path construction takes for a band of this width under a solver kind (host arithmetic only, no device): direct = what
+ * mispec_symshift_path returns, its MISPEC_EINVAL included; auto = the same with 3 in place of the refusal; iterative = 3. */
+int mispec_symshift_solver_path(int64_t n, int64_t half_bandwidth, int solver);
+/* Iterative path: tolerance on the backward error and iteration cap per solve (all passes together); a value <= 0 restores the
+ * default (4e-15, 20000).  MISPEC_EINVAL for a NULL handle or an operator on a direct path. */
+int mispec_symshift_set_iterative(mispec_symshift* S, double tol, int max_iterations);
+/* Iterative path: iterations, passes (1 + restarts) and backward error of the last solve, iterations and solves since
+ * construction (set_shift's probes included), iterations of the last set_shift's probe; zeros on a direct path.  Any output
+ * pointer may be NULL; MISPEC_EINVAL for a NULL handle. */
+int mispec_symshift_iterative_info(const mispec_symshift* S, int64_t* last_iterations, int64_t* total_iterations, int64_t* solves,
+                                   int* last_passes, double* last_backward_error, int64_t* probe_iterations);
 /* General (non-symmetric) form — SparseGenRealShiftSolve (MatOp/SparseGenRealShiftSolve.h:33-99): every stored
  * entry of the CSC / CSR matrix is used; dense factorisation with partial pivoting, n <= 4096. */
 int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
@@ -384,14 +416,15 @@ int mispec_symshift_level_plan(int64_t n, int64_t half_bandwidth, int max_levels
  * (half-bandwidth 65 ... 512 beyond n = 4096); MISPEC_EINVAL when unsupported or for n < 1 or half_bandwidth < 0. */
 int mispec_symshift_path(int64_t n, int64_t half_bandwidth);
 /* The path of this operator (valid after construction) and, on path 2, the block layout: rows per block s, number of blocks
- * ceil(n / s), bytes of the factor kept in HBM after set_shift (16 blocks s^2); zeros on paths 0 and 1.  path is -1 for an operator
- * that set_shift will refuse.  Any output pointer may be NULL. */
+ * ceil(n / s), bytes of the factor kept in HBM after set_shift (16 blocks s^2); zeros on paths 0, 1 and 3 (the iterative path).
+ * path is -1 for an operator that set_shift will refuse.  Any output pointer may be NULL. */
 int mispec_symshift_path_info(const mispec_symshift* S, int* path, int64_t* block_rows, int64_t* blocks, int64_t* factor_bytes);
 /* set_shift(sigma) (SparseSymShiftSolve.h:85-95): MISPEC_EINVAL "factorization failed with the given shift" on breakdown */
 int mispec_symshift_set_shift(mispec_symshift* S, double sigma);
 int mispec_symshift_solve(const mispec_symshift* S, const double* x_dev, double* y_dev);        /* device pointers */
 /* What the last set_shift() of a banded operator found: iterative-refinement steps per solve (0 for a definite
- * A - sigma I), pivots boosted, smallest |pivot| relative to the level's scale, backward error of the probe solve.
+ * A - sigma I), pivots boosted, smallest |pivot| relative to the level's scale, backward error of the probe solve (the iterative
+ * path: zeros and the probe's backward error).
  * Any output pointer may be NULL.  (No reference counterpart: Eigen::SparseLU pivots instead.) */
 int mispec_symshift_refinement_info(const mispec_symshift* S, int* refine_steps, int64_t* boosted_pivots,
                                     double* min_pivot_ratio, double* probe_backward_error);
@@ -401,7 +434,7 @@ int mispec_symshift_solve_host(const mispec_symshift* S, const double* x_host, d
  * 2 | 4 cap the width, 0 allows none), each of which reads the factor once where a panel kernel exists: the narrow-band
  * partitioned levels (half-bandwidth <= 8: sweeps, explicit chunk inverses, separator right-hand sides, back substitution) and the
  * dense inverses (n <= 4096, last level).  Wide levels (half-bandwidth 9 ... 64) and remaining single columns run the single
- * kernels per column; the block-tridiagonal path runs every column on its own whatever shift_block says.  Every column has
+ * kernels per column; the block-tridiagonal and the iterative path run every column on its own whatever shift_block says.  Every column has
  * exactly the bits mispec_symshift_solve gives for it alone, on every path (pencils,
  * reordered matrices, general operators, indefinite shifts with their refinement steps).
  * MISPEC_EINVAL: NULL pointer, k < 1, ldx < n or ldy < n; MISPEC_ELOGIC: set_shift has not been called. */

@@ -21,7 +21,7 @@ __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatP
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
            "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "shift_block_plan", "dia_sym_plan", "mirror_triangle_device",
-           "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub"]
+           "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub", "shift_solver_path"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -276,10 +276,47 @@ class _ShiftBlock:
 
     def path_info(self):
         """{path, block_rows, blocks, factor_bytes} (mispec_symshift_path_info): path 0 = explicit inverse, 1 = chunk path, 2 = the
-        block-tridiagonal path with its block layout and the bytes of its factor (zeros on the other paths), -1 = unsupported."""
+        block-tridiagonal path with its block layout and the bytes of its factor (zeros on the other paths), 3 = the iterative path,
+        -1 = unsupported."""
         p, s, nb, fb = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(lib().mispec_symshift_path_info(self.h, C.byref(p), C.byref(s), C.byref(nb), C.byref(fb)))
         return {"path": p.value, "block_rows": s.value, "blocks": nb.value, "factor_bytes": fb.value}
+
+
+    def set_iterative(self, tol=0.0, max_iterations=0):
+        """Iterative path: tolerance on a solve's backward error and iteration cap per solve; a value <= 0 restores the default
+        (4e-15, 20000).  mispec_symshift_set_iterative."""
+        check(lib().mispec_symshift_set_iterative(self.h, float(tol), int(max_iterations)))
+
+    def iterative_info(self):
+        """Iterative path: {last_iterations, total_iterations, solves, last_passes, last_backward_error, probe_iterations}
+        (mispec_symshift_iterative_info); zeros on a direct path."""
+        li, ti, so, pi = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        lp, om = C.c_int(0), C.c_double(0.0)
+        check(lib().mispec_symshift_iterative_info(self.h, C.byref(li), C.byref(ti), C.byref(so), C.byref(lp), C.byref(om), C.byref(pi)))
+        return {"last_iterations": li.value, "total_iterations": ti.value, "solves": so.value, "last_passes": lp.value,
+                "last_backward_error": om.value, "probe_iterations": pi.value}
+
+
+SHIFT_SOLVERS = {"direct": 0, "auto": 1, "iterative": 2}
+
+
+def _shift_solver_kind(solver):
+    """None (what option shift_solver says) or one of direct | auto | iterative -> the solver kind of include/mispec.h."""
+    if solver is None:
+        return -1
+    if solver not in SHIFT_SOLVERS:
+        raise ValueError("unknown shift solver %r: one of %s" % (solver, ", ".join(SHIFT_SOLVERS)))
+    return SHIFT_SOLVERS[solver]
+
+
+def shift_solver_path(n, half_bandwidth, solver=None):
+    """The path a shift-and-invert operator of this size and half-bandwidth takes under a solver kind (mispec_symshift_solver_path;
+    host only): 0 inverse, 1 chunk, 2 block-tridiagonal, 3 iterative; ValueError where construction would refuse."""
+    rc = lib().mispec_symshift_solver_path(int(n), int(half_bandwidth), _shift_solver_kind(solver))
+    if rc < 0:
+        check(rc)
+    return rc
 
 
 def dia_sym_plan(offsets, reach=-1):
@@ -650,16 +687,17 @@ def _synth(cls, n, offsets, seed, symmetric, ctx):
 
 
 class SparseSymShiftSolve(_ShiftBlock):
-    """MatOp/SparseSymShiftSolve.h: y = (A - sigma I)^{-1} x, solved on the GPU after set_shift(sigma)."""
+    """MatOp/SparseSymShiftSolve.h: y = (A - sigma I)^{-1} x, solved on the GPU after set_shift(sigma).  solver: None (what option
+    shift_solver says; its default is direct) | "direct" | "auto" | "iterative" (include/mispec.h mispec_symshift_create_solver)."""
 
-    def __init__(self, mat, uplo="L", ctx=None):
+    def __init__(self, mat, uplo="L", ctx=None, solver=None):
         self.ctx = ctx or default_context()
         n, nc, outer, inner, val, row_major = _compressed(mat)
         if n != nc:
             raise ValueError("SparseSymShiftSolve: matrix must be square")
         h = C.c_void_p()
-        check(lib().mispec_symshift_create(self.ctx.h, n, _ip(outer), _ip(inner), _dp(val), uplo.encode()[0:1], int(row_major),
-                                           C.byref(h)))
+        check(lib().mispec_symshift_create_solver(self.ctx.h, n, _ip(outer), _ip(inner), _dp(val), uplo.encode()[0:1], int(row_major),
+                                                  _shift_solver_kind(solver), C.byref(h)))
         self.h = h
         self.n = n
 
@@ -886,17 +924,19 @@ class SparseCholesky:
 
 
 class SymShiftInvert(_ShiftBlock):
-    """MatOp/SymShiftInvert.h (sparse A, sparse B): y = (A - sigma B)^{-1} x, factored on the GPU at set_shift(sigma)."""
+    """MatOp/SymShiftInvert.h (sparse A, sparse B): y = (A - sigma B)^{-1} x, factored on the GPU at set_shift(sigma).  solver: as for
+    SparseSymShiftSolve."""
 
-    def __init__(self, A, B, uplo_a="L", uplo_b="L", ctx=None):
+    def __init__(self, A, B, uplo_a="L", uplo_b="L", ctx=None, solver=None):
         self.ctx = ctx or default_context()
         n, nc, ao, ai, av, arm = _compressed(A)
         nb, ncb, bo, bi, bv, brm = _compressed(B)
         if n != nc or nb != n or ncb != n:
             raise ValueError("SymShiftInvert: A and B must be square matrices of the same size")
         h = C.c_void_p()
-        check(lib().mispec_symshift_create_pencil(self.ctx.h, n, _ip(ao), _ip(ai), _dp(av), uplo_a.encode()[0:1], int(arm),
-                                                  _ip(bo), _ip(bi), _dp(bv), uplo_b.encode()[0:1], int(brm), C.byref(h)))
+        check(lib().mispec_symshift_create_pencil_solver(self.ctx.h, n, _ip(ao), _ip(ai), _dp(av), uplo_a.encode()[0:1], int(arm),
+                                                         _ip(bo), _ip(bi), _dp(bv), uplo_b.encode()[0:1], int(brm),
+                                                         _shift_solver_kind(solver), C.byref(h)))
         self.h = h
         self.n = n
 

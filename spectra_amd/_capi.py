@@ -114,6 +114,12 @@ SIGNATURES = {
     "mispec_symshift_path": (C.c_int, [C.c_int64, C.c_int64]),
     "mispec_symshift_path_info": (C.c_int, [_vp, C.POINTER(C.c_int), _lp, _lp, _lp]),
     "mispec_symshift_create": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_char, C.c_int, _vpp]),
+    "mispec_symshift_create_solver": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_char, C.c_int, C.c_int, _vpp]),
+    "mispec_symshift_create_pencil_solver": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_char, C.c_int, _ip, _ip, _dp, C.c_char, C.c_int,
+                                                        C.c_int, _vpp]),
+    "mispec_symshift_solver_path": (C.c_int, [C.c_int64, C.c_int64, C.c_int]),
+    "mispec_symshift_set_iterative": (C.c_int, [_vp, C.c_double, C.c_int]),
+    "mispec_symshift_iterative_info": (C.c_int, [_vp, _lp, _lp, _lp, C.POINTER(C.c_int), _dp, _lp]),
     "mispec_symshift_destroy": (C.c_int, [_vp]),
     "mispec_symshift_rows": (C.c_int64, [_vp]),
     "mispec_symshift_bandwidth": (C.c_int, [_vp, _lp, _lp, C.POINTER(C.c_int)]),

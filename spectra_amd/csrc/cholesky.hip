@@ -44,7 +44,7 @@ extern "C" int mispec_cholesky_create(mispec_ctx* ctx, int64_t n, const int32_t*
         {
             // banded B: the partitioned band factorisation with sigma = 0, keeping the triangular halves
             mispec_symshift* S = nullptr;
-            if (mispec_symshift_create(ctx, n, outer, inner, val, uplo, row_major, &S) != MISPEC_OK)
+            if (mispec_symshift_create_solver(ctx, n, outer, inner, val, uplo, row_major, 0, &S) != MISPEC_OK)  // direct: never option shift_solver
                 throw Error(MISPEC_EINVAL, mispec_last_error());
             C->band = S;
             // (rounds 2-5: half-bandwidth <= 8 only; round 6: the triangular halves run on the wave-per-chunk solve of the wide

@@ -145,7 +145,7 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 enum class Opt
 {
     orth, one_reduction, orth_kernel, host_turn, small, restart_sync, host_steps, overlap, csr_win, spec_corr, exchange, reorder,
-    spmv_staged, spmv_tiles, spmm, dia_sym, host_threads, shift, shift_block, count
+    spmv_staged, spmv_tiles, spmm, dia_sym, host_threads, shift, shift_block, shift_solver, count
 };
 // the values of the choice options, in the order of their entries' lists (`unset` is no value: the option not given)
 enum class Orth { onesweep, onesweep_eager, reference, onesweep_wide };
@@ -158,6 +158,9 @@ enum class Tri { automatic, off, on };  // auto | 0 | 1
 enum class DiaSym { automatic, off, all };  // auto | 0 | all: which symmetric diagonals the diagonal format mirrors (csr_dia.hip)
 enum class Spmm { automatic, off, w2, w4, w8 };  // auto | 0 | 2 | 4 | 8: the widest panel of a block product (spmm.hip)
 enum class ShiftBlock { automatic, off, w2, w4 };  // auto | 0 | 2 | 4: the widest panel of a block shift solve (shiftsolve.hip)
+// direct | auto | iterative: the paths a shift-and-invert operator may take (shiftsolve.hip, shift_minres.hip); the values are the
+// solver kinds of mispec_symshift_create_solver
+enum class ShiftSolverKind { direct, automatic, iterative };
 // choice option: its value as the enum above, `unset` when it is neither set nor in the environment
 int option_choice(Opt o);  // the index of the value in the entry's list, -1 when unset
 template <typename E>
@@ -179,6 +182,7 @@ struct ShiftOptions
     int factor_host = 0;      // factor=host | device: the top level factored on the host / by k_chunk_factor
     int wave = 1;             // 0: the lane-per-chunk kernels for the host-factored wide levels
     int profile = 0;          // 1: set_shift's phases on stderr
+    int minres_check = 16;    // 1 ... 64 iterations the iterative path enqueues between two reads of its stop flag
 };
 ShiftOptions shift_options();
 

@@ -81,6 +81,9 @@ constexpr OptionEntry kOptions[] = {
     {Opt::shift, "shift", "MISPEC_SHIFT", Kind::shift, {}, 0, 0, "kernel variants of the banded shift solve"},
     {Opt::shift_block, "shift_block", "MISPEC_SHIFT_BLOCK", Kind::choice, {"auto", "0", "2", "4"}, 0, 0,
      "widest panel of a block shift solve (0: one solve per column)"},
+    {Opt::shift_solver, "shift_solver", "MISPEC_SHIFT_SOLVER", Kind::choice, {"direct", "auto", "iterative"}, 0, 0,
+     "shift-and-invert operators constructed afterwards: the direct paths only, the iterative path (shift_minres.hip) where "
+     "there is no direct one, or the iterative path always (default direct)"},
 };
 static_assert(sizeof(kOptions) / sizeof(kOptions[0]) == size_t(Opt::count), "one entry per option");
 constexpr bool entries_in_order()
@@ -98,6 +101,7 @@ struct ShiftKey
     const char* key;
     const char* values[kMaxValues];
     int ShiftOptions::*field;
+    int lo = 0, hi = kMaxInt;  // no list: the accepted range
 };
 const ShiftKey kShiftKeys[] = {
     {"lds", {"0", "1"}, &ShiftOptions::lds},
@@ -107,6 +111,7 @@ const ShiftKey kShiftKeys[] = {
     {"factor", {"device", "host"}, &ShiftOptions::factor_host},
     {"wave", {"0", "1"}, &ShiftOptions::wave},
     {"profile", {"0", "1"}, &ShiftOptions::profile},
+    {"minres_check", {}, &ShiftOptions::minres_check, 1, 64},
 };
 
 struct OptionValues
@@ -190,7 +195,9 @@ std::string join(const char* const (&values)[kMaxValues], const char* sep)
         accepted = "a comma list of";
         for (const ShiftKey& k : kShiftKeys)
             accepted += std::string(&k == kShiftKeys ? " " : ", ") + k.key + "=" +
-                        (k.values[0] ? join(k.values, "|") : "<integer from 0 on>");
+                        (k.values[0] ? join(k.values, "|")
+                                     : k.hi == kMaxInt ? std::string("<integer from 0 on>")
+                                                       : "<integer from " + std::to_string(k.lo) + " to " + std::to_string(k.hi) + ">");
         accepted += ", each key at most once";
     }
     throw Error(MISPEC_EINVAL, std::string(origin) + ": '" + v + "' is not a value of option " + e.name + " (" + e.meaning +
@@ -214,7 +221,7 @@ ShiftOptions parse_shift(const std::string& spec, const char* origin)
         const std::string v = key ? item.substr(eq + 1) : item;
         int x = 0;
         const int i = key ? index_of(key->values, v) : -1;
-        const bool number = parse_int(v, 0, kMaxInt, x);
+        const bool number = parse_int(v, key ? key->lo : 0, key ? key->hi : kMaxInt, x);
         if (!key || (seen & bit) || (key->values[0] ? i < 0 : !number))
             reject(kOptions[size_t(Opt::shift)], origin, spec);
         s.*key->field = number ? x : i;

@@ -1848,7 +1848,10 @@ int fac_create_impl(mispec_ctx* ctx, const mispec_csr* A, const mispec_symshift*
             F->h_flag.alloc(8);
             F->h_flag.p[0] = 0;
             F->h_up.alloc(size_t(ncv) * ncv + 2 * size_t(ncv));
-            F->device_steps = !option_flag(Opt::host_steps, false);
+            // An operator on the iterative path (shift_minres.hip) takes its steps host-driven: in a device-driven sweep the steps
+            // behind a stop decision are predicated off, and a Krylov solve enqueued in such a step would iterate on stale vectors
+            // and could report non-convergence for a step that never counts.
+            F->device_steps = !option_flag(Opt::host_steps, false) && !(S && S->path() == ShiftPath::iterative);
             {
                 // default since round 4: the one-sweep steps (every gate of tests/test_gpu_onesweep.py and the reference's own test
                 // programs hold in both modes); MISPEC_ORTH=reference restores the reference's two-pass control flow everywhere

@@ -624,6 +624,10 @@ extern "C" int mispec_lobpcg_set_preconditioner_solver(mispec_lobpcg* S, const m
         {
             MISPEC_REQUIRE(F->ctx == S->ctx && F->n == S->be.n, "LOBPCGSolver: the preconditioner must be a solver of A's size and context");
             MISPEC_REQUIRE(!F->general, "LOBPCGSolver: the preconditioner must be a symmetric solver");
+            // deliberate limit: a truncated Krylov solve is not a fixed linear operator, and its definiteness is not known
+            MISPEC_REQUIRE(F->path() != mispec::ShiftPath::iterative,
+                           "LOBPCGSolver: an operator on the iterative shift-solve path cannot be the preconditioner (a truncated Krylov "
+                           "solve is not a fixed linear operator); use a direct shift solve or the Jacobi preconditioner");
             MISPEC_REQUIRE(!F->factored || F->dense || F->negative_pivots == 0,
                            "LOBPCGSolver: the preconditioner must be positive definite (the factorisation met negative pivots)");
         }

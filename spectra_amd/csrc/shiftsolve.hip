@@ -33,6 +33,7 @@
 // once — K = 4 and 2 for the narrow levels and the dense inverses, K = 1 per column elsewhere; every column has the bits of a single
 // solve.
 #include "shiftsolve.hpp"
+#include "shift_minres.hpp"
 #include "reorder.hpp"
 #include "dense.hpp"
 
@@ -2349,6 +2350,12 @@ void perm_scratch(const mispec_symshift& S)
 template <int K>
 void shiftsolve(const mispec_symshift& S, const double* X, int64_t ldx, double* Y, int64_t ldy)
 {
+    if (S.minres)  // iterative path: one MINRES solve per column, in the caller's index order
+    {
+        for (int c = 0; c < K; c++)
+            minres_solve(S, X + c * ldx, Y + c * ldy);
+        return;
+    }
     if (S.dense)
     {
         launch_row_gemv_panel(*S.ctx, S.inverse.p, S.n, S.n, S.n, X, ldx, K, Y, ldy);
@@ -2376,6 +2383,12 @@ void shiftsolve(const mispec_symshift& S, const double* X, int64_t ldx, double* 
             from_stored_order(S, y + c * ly, Y + c * ldy);
 }
 }  // namespace
+
+void launch_probe_fill(const mispec_ctx& ctx, int64_t n, double* v_dev)
+{
+    hipLaunchKernelGGL(k_probe_fill, row_blocks(n), dim3(kThreads), 0, ctx.stream, n, v_dev);
+    MISPEC_HIP(hipGetLastError());
+}
 
 void launch_shiftsolve(const mispec_symshift& S, const double* x_dev, double* y_dev)
 {
@@ -2443,8 +2456,8 @@ void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int6
     MISPEC_REQUIRE(ldx >= S.n && ldy >= S.n, "mispec_symshift_solve_block: leading dimension too small");
     if (!S.factored)
         throw Error(MISPEC_ELOGIC, "SparseSymShiftSolve: need to call set_shift() first");
-    // the block-tridiagonal path has no panel kernels: the column loop whatever shift_block says
-    const std::vector<int> widths = S.blocktri ? std::vector<int>(size_t(k), 1) : shiftsolve_block_plan(k, 0);
+    // the block-tridiagonal and the iterative path have no panel kernels: the column loop whatever shift_block says
+    const std::vector<int> widths = (S.blocktri || S.minres) ? std::vector<int>(size_t(k), 1) : shiftsolve_block_plan(k, 0);
     if (widths[0] > 1)
         block_scratch(S);
     int c = 0;
@@ -2523,11 +2536,25 @@ void for_each_entry(const TriangleInput& T, int64_t n, Fn&& fn)
         }
 }
 
-int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, const TriangleInput* B, mispec_symshift** out)
+// the solver kind of an operator: what the argument says, -1 = what option shift_solver says (unset: direct)
+ShiftSolverKind solver_kind(int solver)
+{
+    MISPEC_REQUIRE(solver >= -1 && solver <= 2, "mispec_symshift_create_solver: solver is one of -1 (option shift_solver), 0 direct, 1 auto, 2 iterative");
+    return solver < 0 ? option_choice(Opt::shift_solver, ShiftSolverKind::direct) : ShiftSolverKind(solver);
+}
+
+TriangleView view_of(const TriangleInput* T)
+{
+    return T ? TriangleView{T->outer, T->inner, T->val, T->lower ? 'L' : 'U', T->row_major ? 1 : 0} : TriangleView{nullptr, nullptr, nullptr, 'L', 0};
+}
+
+// solver: -1 = what option shift_solver says, 0 direct (never reads the option), 1 auto, 2 iterative
+int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, const TriangleInput* B, mispec_symshift** out, int solver)
 {
     return guarded([&] {
         MISPEC_REQUIRE(ctx && out && A.outer && n >= 1, "mispec_symshift_create: bad argument");
         MISPEC_REQUIRE(ctx->comm.allgather == nullptr, "mispec_symshift_create: shift-and-invert operators cannot be row-sharded");
+        const ShiftSolverKind kind = solver_kind(solver);
         auto S = std::make_unique<mispec_symshift>();
         S->ctx = ctx;
         S->n = n;
@@ -2547,7 +2574,7 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
         std::vector<int32_t> inv;  // old -> new when the matrix is reordered
         // (the adjacency below holds every off-diagonal entry of A and of B twice behind int32 row pointers: a pencil with more
         // entries than that is not reordered — it ends as the clean "unsupported pattern" error instead — ADVICE r05)
-        if (!band_path(n, S->half_bandwidth) && n > kMaxDense && n < (int64_t(1) << 31) &&
+        if (kind != ShiftSolverKind::iterative && !band_path(n, S->half_bandwidth) && n > kMaxDense && n < (int64_t(1) << 31) &&
             2 * (countA + countB) < (int64_t(1) << 31) && option_choice(Opt::reorder, Reorder::automatic) != Reorder::none)
         {
             // Too wide for the band kernels as it comes and too large for the dense path: try a bandwidth-reducing ordering
@@ -2601,7 +2628,12 @@ int symshift_create_impl(mispec_ctx* ctx, int64_t n, const TriangleInput& A, con
             }
         }
         const ShiftPath path = shift_path(n, S->half_bandwidth);
-        if (path == ShiftPath::chunk || path == ShiftPath::blocktri)
+        if (kind == ShiftSolverKind::iterative || (kind == ShiftSolverKind::automatic && path == ShiftPath::unsupported))
+        {
+            // ... the iterative path: the SpMV's own operators of A (and B), no band and no triplets (shift_minres.hip)
+            minres_create(*S, view_of(&A), view_of(B));
+        }
+        else if (path == ShiftPath::chunk || path == ShiftPath::blocktri)
         {
             // ... then, for a band, the band itself (assembled once; every set_shift() starts from it)
             S->band_b = int(std::max<int64_t>(1, std::min<int64_t>(S->half_bandwidth, n - 1)));  // a diagonal matrix: width 1, zeros
@@ -2670,8 +2702,8 @@ bool parse_uplo(char uplo, bool& lower)
 }
 }  // namespace
 
-extern "C" int mispec_symshift_create(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val,
-                                      char uplo, int row_major, mispec_symshift** out)
+extern "C" int mispec_symshift_create_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val,
+                                             char uplo, int row_major, int solver, mispec_symshift** out)
 {
     bool lower;
     if (!parse_uplo(uplo, lower))
@@ -2679,7 +2711,12 @@ extern "C" int mispec_symshift_create(mispec_ctx* ctx, int64_t n, const int32_t*
         set_last_error("mispec_symshift_create: uplo must be 'L' or 'U'");
         return MISPEC_EINVAL;
     }
-    return symshift_create_impl(ctx, n, TriangleInput{outer, inner, val, lower, row_major != 0}, nullptr, out);
+    return symshift_create_impl(ctx, n, TriangleInput{outer, inner, val, lower, row_major != 0}, nullptr, out, solver);
+}
+extern "C" int mispec_symshift_create(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val,
+                                      char uplo, int row_major, mispec_symshift** out)
+{
+    return mispec_symshift_create_solver(ctx, n, outer, inner, val, uplo, row_major, -1, out);
 }
 
 // SparseGenRealShiftSolve (MatOp/SparseGenRealShiftSolve.h:33-99): y = (A - sigma I)^{-1} x for a general sparse A.
@@ -2716,6 +2753,15 @@ extern "C" int mispec_symshift_create_pencil(mispec_ctx* ctx, int64_t n, const i
                                              const int32_t* b_inner, const double* b_val, char b_uplo, int b_row_major,
                                              mispec_symshift** out)
 {
+    return mispec_symshift_create_pencil_solver(ctx, n, a_outer, a_inner, a_val, a_uplo, a_row_major, b_outer, b_inner, b_val, b_uplo,
+                                                b_row_major, -1, out);
+}
+
+extern "C" int mispec_symshift_create_pencil_solver(mispec_ctx* ctx, int64_t n, const int32_t* a_outer, const int32_t* a_inner,
+                                                    const double* a_val, char a_uplo, int a_row_major, const int32_t* b_outer,
+                                                    const int32_t* b_inner, const double* b_val, char b_uplo, int b_row_major,
+                                                    int solver, mispec_symshift** out)
+{
     bool la, lb;
     if (!parse_uplo(a_uplo, la) || !parse_uplo(b_uplo, lb) || !b_outer)
     {
@@ -2723,7 +2769,7 @@ extern "C" int mispec_symshift_create_pencil(mispec_ctx* ctx, int64_t n, const i
         return MISPEC_EINVAL;
     }
     const TriangleInput B{b_outer, b_inner, b_val, lb, b_row_major != 0};
-    return symshift_create_impl(ctx, n, TriangleInput{a_outer, a_inner, a_val, la, a_row_major != 0}, &B, out);
+    return symshift_create_impl(ctx, n, TriangleInput{a_outer, a_inner, a_val, la, a_row_major != 0}, &B, out, solver);
 }
 
 extern "C" int mispec_symshift_destroy(mispec_symshift* S)
@@ -2763,6 +2809,24 @@ extern "C" int mispec_symshift_path(int64_t n, int64_t half_bandwidth)
         path = int(p);
     });
     return rc == MISPEC_OK ? path : rc;
+}
+
+// The path construction takes for a band of that width under a solver kind (no device needed): direct = mispec_symshift_path,
+// its refusal included; auto = the same with the iterative path in place of the refusal; iterative = 3.
+extern "C" int mispec_symshift_solver_path(int64_t n, int64_t half_bandwidth, int solver)
+{
+    int path = 0;
+    const int rc = guarded([&] {
+        MISPEC_REQUIRE(n >= 1 && half_bandwidth >= 0, "mispec_symshift_solver_path: bad argument");
+        const ShiftSolverKind kind = solver_kind(solver);
+        const ShiftPath p = shift_path(n, half_bandwidth);
+        path = int(kind == ShiftSolverKind::iterative || (kind == ShiftSolverKind::automatic && p == ShiftPath::unsupported)
+                       ? ShiftPath::iterative
+                       : p);
+    });
+    if (rc != MISPEC_OK)
+        return rc;
+    return path == int(ShiftPath::unsupported) ? mispec_symshift_path(n, half_bandwidth) : path;
 }
 
 extern "C" int mispec_symshift_path_info(const mispec_symshift* S, int* path, int64_t* block_rows, int64_t* blocks, int64_t* factor_bytes)
@@ -2840,7 +2904,15 @@ extern "C" int mispec_symshift_set_shift(mispec_symshift* S, double sigma)
         S->sigma = sigma;
         const int64_t n = S->n;
         const ShiftPath path = S->path();
-        if (path == ShiftPath::blocktri)
+        if (path == ShiftPath::iterative)
+        {
+            // O(n) work and one probe solve; a shift the probe cannot be solved for is refused here, where the direct paths say
+            // "factorization failed with the given shift"
+            S->dense = false;
+            PhaseTimer pt("minres_set_shift (preconditioner, probe solve)", n, 0);
+            minres_set_shift(*S, sigma);
+        }
+        else if (path == ShiftPath::blocktri)
         {
             // the whole chain is enqueued and its record read once (shift_blocktri.hip); interior shifts get the chunk path's
             // calibrated refinement with this factorisation's solve

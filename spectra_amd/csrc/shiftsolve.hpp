@@ -15,8 +15,9 @@ inline bool band_path(int64_t n, int64_t b) { return b <= kNarrowBandwidth || (b
 constexpr int64_t kMaxBlockBandwidth = 512;  // block-tridiagonal path: one s x s block (s = half-bandwidth) is 2 MiB of an XCD's 4 MiB L2
 // The path of (n, b), for every site that decides one: the chunk path where band_path says so, else the explicit inverse up to
 // kMaxDense, else the block-tridiagonal factorisation (shift_blocktri.hip) up to kMaxBlockBandwidth, else none.  The values are
-// those of mispec_symshift_path.
-enum class ShiftPath { unsupported = -1, inverse = 0, chunk = 1, blocktri = 2 };
+// those of mispec_symshift_path.  `iterative` (shift_minres.hip) is never the answer of shift_path: an operator takes it only when
+// its solver kind (option shift_solver, mispec_symshift_create_solver) asks for it.
+enum class ShiftPath { unsupported = -1, inverse = 0, chunk = 1, blocktri = 2, iterative = 3 };
 inline ShiftPath shift_path(int64_t n, int64_t b)
 {
     if (band_path(n, b))
@@ -36,6 +37,7 @@ struct BlockTri
     DevBuf<unsigned long long> record;  // [0] zero pivot columns, [1] bits of the smallest |pivot| / max |S_i|
     size_t factor_bytes() const { return 2 * size_t(N) * size_t(s) * size_t(s) * sizeof(double); }
 };
+struct ShiftMinres;  // the iterative path's operator, vectors and counters (shift_minres.hip)
 }  // namespace mispec
 
 struct mispec_symshift
@@ -65,8 +67,11 @@ struct mispec_symshift
     bool dense = false;
     std::unique_ptr<mispec::BandLevel> top;  // banded path
     std::unique_ptr<mispec::BlockTri> blocktri;  // block-tridiagonal path (65 <= band_b <= 512 beyond the dense limit)
+    std::unique_ptr<mispec::ShiftMinres> minres;  // iterative path: set at construction, no band and no triplets are kept then
     mispec::ShiftPath path() const  // a general (non-symmetric) operator has the explicit inverse only
     {
+        if (minres)
+            return mispec::ShiftPath::iterative;
         if (general)
             return n <= mispec::kMaxDense ? mispec::ShiftPath::inverse : mispec::ShiftPath::unsupported;
         return mispec::shift_path(n, half_bandwidth);
@@ -114,6 +119,24 @@ void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int6
 double blocktri_factor(mispec_symshift& S, double sigma);
 // y = M^{-1} x in stored order with that factor: device pointers of n doubles, 2 N + 1 launches on the context stream
 void blocktri_solve(const mispec_symshift& S, const double* x_dev, double* y_dev);
+// Iterative path (shift_minres.hip): preconditioned MINRES on A - sigma B with the products of the handle's own CSR operators.
+// minres_create builds them from the triangle(s) by the SpMV's ingest (B.outer == nullptr: B = I) and keeps diag and the row sums
+// of |.|; minres_set_shift forms the Jacobi preconditioner and |M|_inf, solves the probe right-hand side and throws MISPEC_EINVAL
+// "... did not converge ..." for a shift it cannot solve; minres_solve is y = (A - sigma B)^{-1} x in the caller's index order and
+// throws MISPEC_ERUNTIME with the same wording.
+struct TriangleView
+{
+    const int32_t* outer;
+    const int32_t* inner;
+    const double* val;
+    char uplo;
+    int row_major;
+};
+void minres_create(mispec_symshift& S, const TriangleView& A, const TriangleView& B);
+void minres_set_shift(mispec_symshift& S, double sigma);
+void minres_solve(const mispec_symshift& S, const double* x_dev, double* y_dev, bool probe = false);
+// the probe right-hand side of set_shift's calibration: deterministic values in (-0.5, 0.5), on the context stream
+void launch_probe_fill(const mispec_ctx& ctx, int64_t n, double* v_dev);
 // the cut of k columns: widths 4 / 2 / 1, widest first.  panel: 0 = what option shift_block says, 1 = single columns, 2 | 4 = the
 // widest panel
 std::vector<int> shiftsolve_block_plan(int k, int panel);
