@@ -31,7 +31,7 @@ public:
     using Scalar = Scalar_;
 
     explicit DenseGenRealShiftSolve(const DenseView<Scalar>& mat, internal::CtxPtr ctx = internal::CtxPtr()) :
-        Base(internal::CompressedCopy(checked(mat)).view(), ctx)
+        Base(internal::CompressedCopy(checked(mat)).view(), ctx, ShiftSolver::Direct)  // dense: never the iterative path
     {}
 #ifdef MISPEC_HAVE_EIGEN
     // The reference's constructor: an Eigen matrix or Map of matching storage order (copied once on the host)

@@ -1,7 +1,11 @@
 // y = (A - sigma I)^{-1} x for a general real sparse A — the operator of GenEigsRealShiftSolver (reference:
 // MatOp/SparseGenRealShiftSolve.h:25-100, which factors with Eigen::SparseLU).  Same members: rows(), cols(),
 // set_shift(), perform_op().  The device factorisation is the dense one (LU with partial pivoting, explicit
-// inverse in HBM, GEMV per application): n <= 4096.
+// inverse in HBM, GEMV per application): n <= 4096.  Beyond that the constructor throws std::invalid_argument, unless the operator
+// is constructed with ShiftSolver::Auto or ShiftSolver::Iterative (or option shift_solver says so): it then applies
+// (A - sigma I)^{-1} by Jacobi-preconditioned BiCGStab on the SpMV's own operator (csrc/shift_bicgstab.hip), every solve to a
+// backward error of 4e-15; set_shift() refuses a shift whose probe solve does not converge, perform_op() throws
+// std::runtime_error for a solve that does not.
 #ifndef MISPEC_SPECTRA_SPARSE_GEN_REAL_SHIFT_SOLVE_H
 #define MISPEC_SPECTRA_SPARSE_GEN_REAL_SHIFT_SOLVE_H
 
@@ -25,7 +29,7 @@ private:
     internal::CtxPtr m_ctx;
     std::shared_ptr<mispec_symshift> m_solver;
 
-    void ingest(const SparseView<Scalar, StorageIndex>& A)
+    void ingest(const SparseView<Scalar, StorageIndex>& A, ShiftSolver solver)
     {
         if (A.rows != A.cols)
             throw std::invalid_argument("SparseGenRealShiftSolve: matrix must be square");
@@ -35,20 +39,23 @@ private:
         mispec_symshift* raw = nullptr;
         const std::size_t nnz = static_cast<std::size_t>(A.outer[A.rows]);
         const internal::Int32Indices<StorageIndex> outer(A.outer, static_cast<std::size_t>(A.rows) + 1), inner(A.inner, nnz);
-        internal::check(mispec_symshift_create_general(m_ctx.get(), A.rows, outer.data(), inner.data(), A.values, A.row_major ? 1 : 0, &raw));
+        internal::check(mispec_symshift_create_general_solver(m_ctx.get(), A.rows, outer.data(), inner.data(), A.values, A.row_major ? 1 : 0,
+                                                              static_cast<int>(solver), &raw));
         m_solver = std::shared_ptr<mispec_symshift>(raw, [](mispec_symshift* p) { (void) mispec_symshift_destroy(p); });
     }
 
 public:
-    explicit SparseGenRealShiftSolve(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx = internal::CtxPtr()) :
+    explicit SparseGenRealShiftSolve(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx = internal::CtxPtr(),
+                                     ShiftSolver solver = ShiftSolver::Default) :
         m_ctx(ctx ? ctx : internal::default_context())
     {
-        ingest(mat);
+        ingest(mat, solver);
     }
 
 #ifdef MISPEC_HAVE_EIGEN
     template <typename Derived>
-    SparseGenRealShiftSolve(const Eigen::SparseMatrixBase<Derived>& mat) : m_ctx(internal::default_context())
+    SparseGenRealShiftSolve(const Eigen::SparseMatrixBase<Derived>& mat, ShiftSolver solver = ShiftSolver::Default) :
+        m_ctx(internal::default_context())
     {
         using Plain = Eigen::SparseMatrix<Scalar, Flags, StorageIndex>;
         static_assert(static_cast<int>(Derived::PlainObject::IsRowMajor) == static_cast<int>(Plain::IsRowMajor),
@@ -62,7 +69,7 @@ public:
         v.inner = tmp.innerIndexPtr();
         v.values = tmp.valuePtr();
         v.row_major = Plain::IsRowMajor;
-        ingest(v);
+        ingest(v, solver);
     }
 #endif
 

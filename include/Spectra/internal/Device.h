@@ -14,7 +14,8 @@ namespace Spectra {
 
 // Which paths a shift-and-invert operator (SparseSymShiftSolve, SymShiftInvert) may take — the solver kinds of
 // mispec_symshift_create_solver: Default = what option shift_solver says (direct unless set), Direct = the factorisations only,
-// Auto = a factorisation where construction finds one, else the iterative path (preconditioned MINRES, any sparsity pattern),
+// Auto = a factorisation where construction finds one, else the iterative path (preconditioned MINRES, any sparsity pattern;
+// preconditioned BiCGStab for the general operator of SparseGenRealShiftSolve, mispec_symshift_create_general_solver),
 // Iterative = the iterative path always.
 enum class ShiftSolver
 {

@@ -392,14 +392,32 @@ int mispec_symshift_solver_path(int64_t n, int64_t half_bandwidth, int solver);
  * default (4e-15, 20000).  MISPEC_EINVAL for a NULL handle or an operator on a direct path. */
 int mispec_symshift_set_iterative(mispec_symshift* S, double tol, int max_iterations);
 /* Iterative path: iterations, passes (1 + restarts) and backward error of the last solve, iterations and solves since
- * construction (set_shift's probes included), iterations of the last set_shift's probe; zeros on a direct path.  Any output
+ * construction (set_shift's probes included), iterations of the last set_shift's probe; zeros on a direct path.  One iteration
+ * is one product with A (and B) on a symmetric operator (MINRES) and two products with A on a general one (BiCGStab).  Any output
  * pointer may be NULL; MISPEC_EINVAL for a NULL handle. */
 int mispec_symshift_iterative_info(const mispec_symshift* S, int64_t* last_iterations, int64_t* total_iterations, int64_t* solves,
                                    int* last_passes, double* last_backward_error, int64_t* probe_iterations);
 /* General (non-symmetric) form — SparseGenRealShiftSolve (MatOp/SparseGenRealShiftSolve.h:33-99): every stored
- * entry of the CSC / CSR matrix is used; dense factorisation with partial pivoting, n <= 4096. */
+ * entry of the CSC / CSR matrix is used; dense factorisation with partial pivoting, n <= 4096.  It reads option shift_solver as
+ * the symmetric constructors do (the call below with solver = -1). */
 int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
                                    const double* val_host, int row_major, mispec_symshift** out);
+/* The same with the solver kind of this operator (the values of mispec_symshift_create_solver).  direct: the dense path, n > 4096
+ * refused.  auto: the dense path up to n = 4096, the iterative path beyond.  iterative: that path for every n >= 1.  The ITERATIVE
+ * PATH of a general operator (path 3, as for the symmetric ones; the handle knows its method) applies (A - sigma I)^{-1} by
+ * right-preconditioned BiCGStab with the Jacobi preconditioner 1 / diag(A - sigma I) (signed; entries at most 2^-26 of the
+ * largest are replaced by it) on the SpMV's own operator of A — mispec_csr_upload / mispec_csr_from_csc, so row-major and
+ * column-major input of one matrix give one operator.  Acceptance, restarts, refusal of a shift by set_shift, wording, settings
+ * (mispec_symshift_set_iterative) and counters (mispec_symshift_iterative_info) are those of the symmetric iterative path; an
+ * ITERATION counted there is one BiCGStab iteration, which is TWO products with A (a MINRES iteration is one).  A breakdown of
+ * the recurrence ends a pass and the solve restarts from the explicit residual; it is no error.  No factor and no triplets are
+ * kept: 12 work vectors of n doubles.  mispec_symshift_set_shift_complex refuses such a handle (MISPEC_EINVAL): complex shifts
+ * need the dense path.  The eigensolvers take their steps host-driven on it. */
+int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
+                                          const double* val_host, int row_major, int solver, mispec_symshift** out);
+/* The path mispec_symshift_create_general_solver takes for dimension n under a solver kind (host arithmetic only, no device):
+ * 0 (explicit inverse) or 3 (iterative); MISPEC_EINVAL with the constructor's wording where it refuses (direct, n > 4096). */
+int mispec_symshift_general_solver_path(int64_t n, int solver);
 int mispec_symshift_destroy(mispec_symshift* S);
 int64_t mispec_symshift_rows(const mispec_symshift* S);
 /* half-bandwidth of the matrix as given, of the matrix as stored (after the ordering, if one was adopted), and whether it is stored reordered */

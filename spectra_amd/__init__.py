@@ -21,7 +21,8 @@ __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatP
            "SymEigsShiftSolver", "GenEigsSolver", "SVDMatOp", "PartialSVDSolver", "SparseRegularInverse", "SparseCholesky", "SymGEigsSolver", "SymShiftInvert", "SymGEigsShiftSolver", "SparseGenRealShiftSolve", "GenEigsRealShiftSolver", "shard_block",
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
            "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "shift_block_plan", "dia_sym_plan", "mirror_triangle_device",
-           "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub", "shift_solver_path"]
+           "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub", "shift_solver_path",
+           "general_shift_solver_path"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -282,10 +283,16 @@ class _ShiftBlock:
         check(lib().mispec_symshift_path_info(self.h, C.byref(p), C.byref(s), C.byref(nb), C.byref(fb)))
         return {"path": p.value, "block_rows": s.value, "blocks": nb.value, "factor_bytes": fb.value}
 
+    def refinement_info(self):
+        """Banded path: {refine_steps, boosted_pivots, min_pivot_ratio, probe_backward_error} of the last set_shift()."""
+        st, bo, mr, om = C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        check(lib().mispec_symshift_refinement_info(self.h, C.byref(st), C.byref(bo), C.byref(mr), C.byref(om)))
+        return {"refine_steps": st.value, "boosted_pivots": bo.value, "min_pivot_ratio": mr.value, "probe_backward_error": om.value}
 
     def set_iterative(self, tol=0.0, max_iterations=0):
         """Iterative path: tolerance on a solve's backward error and iteration cap per solve; a value <= 0 restores the default
-        (4e-15, 20000).  mispec_symshift_set_iterative."""
+        (4e-15, 20000).  mispec_symshift_set_iterative.  An iteration is one product on a symmetric operator (MINRES), two on a
+        general one (BiCGStab)."""
         check(lib().mispec_symshift_set_iterative(self.h, float(tol), int(max_iterations)))
 
     def iterative_info(self):
@@ -314,6 +321,15 @@ def shift_solver_path(n, half_bandwidth, solver=None):
     """The path a shift-and-invert operator of this size and half-bandwidth takes under a solver kind (mispec_symshift_solver_path;
     host only): 0 inverse, 1 chunk, 2 block-tridiagonal, 3 iterative; ValueError where construction would refuse."""
     rc = lib().mispec_symshift_solver_path(int(n), int(half_bandwidth), _shift_solver_kind(solver))
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def general_shift_solver_path(n, solver=None):
+    """The path a general (non-symmetric) shift-and-invert operator of this size takes under a solver kind
+    (mispec_symshift_general_solver_path; host only): 0 inverse, 3 iterative; ValueError where construction would refuse."""
+    rc = lib().mispec_symshift_general_solver_path(int(n), _shift_solver_kind(solver))
     if rc < 0:
         check(rc)
     return rc
@@ -719,12 +735,6 @@ class SparseSymShiftSolve(_ShiftBlock):
         a, b, r = C.c_int64(0), C.c_int64(0), C.c_int(0)
         check(lib().mispec_symshift_bandwidth(self.h, C.byref(a), C.byref(b), C.byref(r)))
         return {"as_given": a.value, "stored": b.value, "reordered": bool(r.value)}
-
-    def refinement_info(self):
-        """Banded path: {refine_steps, boosted_pivots, min_pivot_ratio, probe_backward_error} of the last set_shift()."""
-        st, bo, mr, om = C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-        check(lib().mispec_symshift_refinement_info(self.h, C.byref(st), C.byref(bo), C.byref(mr), C.byref(om)))
-        return {"refine_steps": st.value, "boosted_pivots": bo.value, "min_pivot_ratio": mr.value, "probe_backward_error": om.value}
 
     def perform_op(self, x_in):
         x = _f64(x_in)
@@ -1577,16 +1587,18 @@ class SymEigsShiftSolver(SymEigsSolver):
 
 
 class SparseGenRealShiftSolve(_ShiftBlock):
-    """MatOp/SparseGenRealShiftSolve.h: y = (A - sigma I)^{-1} x for a general sparse A (dense device factorisation,
-    n <= 4096)."""
+    """MatOp/SparseGenRealShiftSolve.h: y = (A - sigma I)^{-1} x for a general sparse A.  solver: None (what option shift_solver
+    says; its default is direct) | "direct" (dense device factorisation, n <= 4096) | "auto" (that, and beyond n = 4096 the
+    iterative path: Jacobi-preconditioned BiCGStab) | "iterative" (include/mispec.h mispec_symshift_create_general_solver)."""
 
-    def __init__(self, mat, ctx=None):
+    def __init__(self, mat, ctx=None, solver=None):
         self.ctx = ctx or default_context()
         n, nc, outer, inner, val, row_major = _compressed(mat)
         if n != nc:
             raise ValueError("SparseGenRealShiftSolve: matrix must be square")
         h = C.c_void_p()
-        check(lib().mispec_symshift_create_general(self.ctx.h, n, _ip(outer), _ip(inner), _dp(val), int(row_major), C.byref(h)))
+        check(lib().mispec_symshift_create_general_solver(self.ctx.h, n, _ip(outer), _ip(inner), _dp(val), int(row_major),
+                                                          _shift_solver_kind(solver), C.byref(h)))
         self.h = h
         self.n = n
 
@@ -1606,6 +1618,10 @@ class SparseGenRealShiftSolve(_ShiftBlock):
         y = np.empty(self.n)
         check(lib().mispec_symshift_solve_host(self.h, _dp(x), _dp(y)))
         return y
+
+    def solve_device(self, x_ptr, y_ptr):
+        """y = (A - sigma I)^{-1} x on device pointers, enqueued on the context's stream (mispec_symshift_solve)."""
+        check(lib().mispec_symshift_solve(self.h, C.c_void_p(int(x_ptr)), C.c_void_p(int(y_ptr))))
 
     def __del__(self):
         try:
@@ -1740,7 +1756,14 @@ class GenEigsRealShiftSolver(GenEigsSolver):
         super().__init__(_GenShiftBinding(op, sigma), nev, ncv)
 
 class SparseGenComplexShiftSolve(SparseGenRealShiftSolve):
-    """MatOp/SparseGenComplexShiftSolve.h: y = Re((A - sigma I)^{-1} x) for a general sparse A and a complex shift (n <= 4096)."""
+    """MatOp/SparseGenComplexShiftSolve.h: y = Re((A - sigma I)^{-1} x) for a general sparse A and a complex shift (n <= 4096).
+    The dense path only: a solver kind other than direct is refused, and option shift_solver is not read."""
+
+    def __init__(self, mat, ctx=None, solver=None):
+        if solver not in (None, "direct"):
+            raise ValueError("SparseGenComplexShiftSolve: solver %r is not supported: the iterative path takes real shifts only "
+                             "(complex shifts need the dense path, solver='direct', n <= 4096)" % (solver,))
+        super().__init__(mat, ctx, "direct")
 
     def set_shift(self, sigmar, sigmai=0.0):
         check(lib().mispec_symshift_set_shift_complex(self.h, float(sigmar), float(sigmai)))
@@ -1774,7 +1797,7 @@ class DenseGenRealShiftSolve(SparseGenRealShiftSolve):
     """MatOp/DenseGenRealShiftSolve.h: y = (A - sigma I)^{-1} x for a general dense A and a real shift (n <= 4096)."""
 
     def __init__(self, mat, ctx=None):
-        super().__init__(_dense_as_csc(mat, "DenseGenRealShiftSolve"), ctx)
+        super().__init__(_dense_as_csc(mat, "DenseGenRealShiftSolve"), ctx, "direct")  # dense: never the iterative path
 
 
 class DenseGenComplexShiftSolve(SparseGenComplexShiftSolve):
@@ -2073,6 +2096,11 @@ class Factorization:
             self.ctx = op.ctx
             self.n = op.n
             check(lib().mispec_fac_create_device_op(self.ctx.h, op.cb, None, self.n, self.m, int(symmetric), C.byref(h)))
+            self._user = None
+        elif isinstance(op, SparseGenRealShiftSolve):  # Arnoldi on (A - sigma I)^{-1}, bound on the device; call set_shift first
+            self.ctx = op.ctx
+            self.n = op.rows()
+            check(lib().mispec_fac_create_shiftsolve(self.ctx.h, op.h, self.m, int(symmetric), C.byref(h)))
             self._user = None
         else:
             self.ctx = ctx or default_context()

@@ -318,6 +318,8 @@ SIGNATURES = {
     "mispec_geneigs_create_dense": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vpp]),
     "mispec_geneigs_create_device_op": (C.c_int, [_vp, device_op_fn, _vp, C.c_int64, C.c_int64, C.c_int64, _vpp]),
     "mispec_symshift_create_general": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_int, _vpp]),
+    "mispec_symshift_create_general_solver": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_int, C.c_int, _vpp]),
+    "mispec_symshift_general_solver_path": (C.c_int, [C.c_int64, C.c_int]),
     "mispec_geneigs_destroy": (C.c_int, [_vp]),
     "mispec_geneigs_init": (C.c_int, [_vp, _dp]),
     "mispec_geneigs_compute": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_double, C.c_int, _lp]),

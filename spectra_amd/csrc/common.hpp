@@ -182,7 +182,7 @@ struct ShiftOptions
     int factor_host = 0;      // factor=host | device: the top level factored on the host / by k_chunk_factor
     int wave = 1;             // 0: the lane-per-chunk kernels for the host-factored wide levels
     int profile = 0;          // 1: set_shift's phases on stderr
-    int minres_check = 16;    // 1 ... 64 iterations the iterative path enqueues between two reads of its stop flag
+    int minres_check = 16;    // 1 ... 64 iterations the iterative path (MINRES and BiCGStab alike) enqueues between two reads of its stop flag
 };
 ShiftOptions shift_options();
 

@@ -82,7 +82,7 @@ constexpr OptionEntry kOptions[] = {
     {Opt::shift_block, "shift_block", "MISPEC_SHIFT_BLOCK", Kind::choice, {"auto", "0", "2", "4"}, 0, 0,
      "widest panel of a block shift solve (0: one solve per column)"},
     {Opt::shift_solver, "shift_solver", "MISPEC_SHIFT_SOLVER", Kind::choice, {"direct", "auto", "iterative"}, 0, 0,
-     "shift-and-invert operators constructed afterwards: the direct paths only, the iterative path (shift_minres.hip) where "
+     "shift-and-invert operators constructed afterwards: the direct paths only, the iterative path (shift_minres.hip; shift_bicgstab.hip for a general operator) where "
      "there is no direct one, or the iterative path always (default direct)"},
 };
 static_assert(sizeof(kOptions) / sizeof(kOptions[0]) == size_t(Opt::count), "one entry per option");

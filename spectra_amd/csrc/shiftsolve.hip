@@ -33,6 +33,7 @@
 // once — K = 4 and 2 for the narrow levels and the dense inverses, K = 1 per column elsewhere; every column has the bits of a single
 // solve.
 #include "shiftsolve.hpp"
+#include "shift_bicgstab.hpp"
 #include "shift_minres.hpp"
 #include "reorder.hpp"
 #include "dense.hpp"
@@ -2350,10 +2351,13 @@ void perm_scratch(const mispec_symshift& S)
 template <int K>
 void shiftsolve(const mispec_symshift& S, const double* X, int64_t ldx, double* Y, int64_t ldy)
 {
-    if (S.minres)  // iterative path: one MINRES solve per column, in the caller's index order
+    if (S.minres || S.bicgstab)  // iterative path: one Krylov solve per column, in the caller's index order
     {
         for (int c = 0; c < K; c++)
-            minres_solve(S, X + c * ldx, Y + c * ldy);
+            if (S.minres)
+                minres_solve(S, X + c * ldx, Y + c * ldy);
+            else
+                bicgstab_solve(S, X + c * ldx, Y + c * ldy);
         return;
     }
     if (S.dense)
@@ -2457,7 +2461,7 @@ void launch_shiftsolve_block(const mispec_symshift& S, const double* X_dev, int6
     if (!S.factored)
         throw Error(MISPEC_ELOGIC, "SparseSymShiftSolve: need to call set_shift() first");
     // the block-tridiagonal and the iterative path have no panel kernels: the column loop whatever shift_block says
-    const std::vector<int> widths = (S.blocktri || S.minres) ? std::vector<int>(size_t(k), 1) : shiftsolve_block_plan(k, 0);
+    const std::vector<int> widths = (S.blocktri || S.minres || S.bicgstab) ? std::vector<int>(size_t(k), 1) : shiftsolve_block_plan(k, 0);
     if (widths[0] > 1)
         block_scratch(S);
     int c = 0;
@@ -2507,6 +2511,10 @@ void launch_band_cholesky_solve(const mispec_symshift& S, bool upper, const doub
 }  // namespace mispec
 
 mispec_symshift::~mispec_symshift() {}
+mispec::ShiftIterative* mispec_symshift::iterative() const
+{
+    return minres ? static_cast<mispec::ShiftIterative*>(minres.get()) : bicgstab.get();
+}
 
 // =================================================================================================
 // C ABI
@@ -2720,14 +2728,15 @@ extern "C" int mispec_symshift_create(mispec_ctx* ctx, int64_t n, const int32_t*
 }
 
 // SparseGenRealShiftSolve (MatOp/SparseGenRealShiftSolve.h:33-99): y = (A - sigma I)^{-1} x for a general sparse A.
-// The reference factors with Eigen::SparseLU; here the dense path is used (LU with partial pivoting, explicit
-// inverse, GEMV), so n <= 4096.
-extern "C" int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val,
-                                              int row_major, mispec_symshift** out)
+// The reference factors with Eigen::SparseLU; here the dense path is used (LU with partial pivoting, explicit inverse, GEMV) for
+// n <= 4096, and where the solver kind allows it the iterative path (BiCGStab, shift_bicgstab.hip), which keeps no triplets.
+extern "C" int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner,
+                                                     const double* val, int row_major, int solver, mispec_symshift** out)
 {
     return guarded([&] {
         MISPEC_REQUIRE(ctx && out && outer && n >= 1, "mispec_symshift_create_general: bad argument");
-        MISPEC_REQUIRE(n <= kMaxDense,
+        const ShiftPath path = general_shift_path(n, solver_kind(solver));
+        MISPEC_REQUIRE(path != ShiftPath::unsupported,
                        "SparseGenRealShiftSolve: only n <= 4096 is supported on the GPU (the reference uses a general sparse LU)");
         MISPEC_REQUIRE(ctx->comm.allgather == nullptr, "mispec_symshift_create_general: shift-and-invert operators cannot be row-sharded");
         auto S = std::make_unique<mispec_symshift>();
@@ -2735,17 +2744,25 @@ extern "C" int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const 
         S->n = n;
         S->general = true;
         S->half_bandwidth = n;  // never the banded (symmetric) path
-        for (int64_t o = 0; o < n; o++)
-            for (int32_t p = outer[o]; p < outer[o + 1]; p++)
-            {
-                const int64_t in = inner[p];
-                MISPEC_REQUIRE(in >= 0 && in < n, "mispec_symshift_create_general: index out of range");
-                S->rows.push_back(row_major ? o : in);
-                S->cols.push_back(row_major ? in : o);
-                S->vals.push_back(val[p]);
-            }
+        if (path == ShiftPath::iterative)
+            bicgstab_create(*S, outer, inner, val, row_major);
+        else
+            for (int64_t o = 0; o < n; o++)
+                for (int32_t p = outer[o]; p < outer[o + 1]; p++)
+                {
+                    const int64_t in = inner[p];
+                    MISPEC_REQUIRE(in >= 0 && in < n, "mispec_symshift_create_general: index out of range");
+                    S->rows.push_back(row_major ? o : in);
+                    S->cols.push_back(row_major ? in : o);
+                    S->vals.push_back(val[p]);
+                }
         *out = S.release();
     });
+}
+extern "C" int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val,
+                                              int row_major, mispec_symshift** out)
+{
+    return mispec_symshift_create_general_solver(ctx, n, outer, inner, val, row_major, -1, out);
 }
 
 extern "C" int mispec_symshift_create_pencil(mispec_ctx* ctx, int64_t n, const int32_t* a_outer, const int32_t* a_inner,
@@ -2829,6 +2846,21 @@ extern "C" int mispec_symshift_solver_path(int64_t n, int64_t half_bandwidth, in
     return path == int(ShiftPath::unsupported) ? mispec_symshift_path(n, half_bandwidth) : path;
 }
 
+// The same rule for a general operator, which has no band paths: the explicit inverse up to n = 4096 under direct and auto, beyond
+// it the refusal of mispec_symshift_create_general (direct) or the iterative path (auto); iterative = 3 at every n.
+extern "C" int mispec_symshift_general_solver_path(int64_t n, int solver)
+{
+    int path = 0;
+    const int rc = guarded([&] {
+        MISPEC_REQUIRE(n >= 1, "mispec_symshift_general_solver_path: bad argument");
+        const ShiftPath p = general_shift_path(n, solver_kind(solver));
+        MISPEC_REQUIRE(p != ShiftPath::unsupported,
+                       "SparseGenRealShiftSolve: only n <= 4096 is supported on the GPU (the reference uses a general sparse LU)");
+        path = int(p);
+    });
+    return rc == MISPEC_OK ? path : rc;
+}
+
 extern "C" int mispec_symshift_path_info(const mispec_symshift* S, int* path, int64_t* block_rows, int64_t* blocks, int64_t* factor_bytes)
 {
     return guarded([&] {
@@ -2909,8 +2941,11 @@ extern "C" int mispec_symshift_set_shift(mispec_symshift* S, double sigma)
             // O(n) work and one probe solve; a shift the probe cannot be solved for is refused here, where the direct paths say
             // "factorization failed with the given shift"
             S->dense = false;
-            PhaseTimer pt("minres_set_shift (preconditioner, probe solve)", n, 0);
-            minres_set_shift(*S, sigma);
+            PhaseTimer pt(S->minres ? "minres_set_shift (preconditioner, probe solve)" : "bicgstab_set_shift (preconditioner, probe solve)", n, 0);
+            if (S->minres)
+                minres_set_shift(*S, sigma);
+            else
+                bicgstab_set_shift(*S, sigma);
         }
         else if (path == ShiftPath::blocktri)
         {
@@ -3061,6 +3096,8 @@ extern "C" int mispec_symshift_set_shift_complex(mispec_symshift* S, double sigm
     return guarded([&] {
         MISPEC_REQUIRE(S, "mispec_symshift_set_shift_complex: NULL argument");
         MISPEC_REQUIRE(S->general && !S->pencil, "mispec_symshift_set_shift_complex: complex shifts are for the general (non-symmetric) operator");
+        MISPEC_REQUIRE(!S->bicgstab, "SparseGenComplexShiftSolve: the iterative path takes real shifts only (a complex shift needs the dense path: "
+                                     "solver direct, n <= 4096)");
         S->ctx->make_current();
         S->factored = false;
         S->sigma = sigmar;

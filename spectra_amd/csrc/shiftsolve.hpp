@@ -15,8 +15,9 @@ inline bool band_path(int64_t n, int64_t b) { return b <= kNarrowBandwidth || (b
 constexpr int64_t kMaxBlockBandwidth = 512;  // block-tridiagonal path: one s x s block (s = half-bandwidth) is 2 MiB of an XCD's 4 MiB L2
 // The path of (n, b), for every site that decides one: the chunk path where band_path says so, else the explicit inverse up to
 // kMaxDense, else the block-tridiagonal factorisation (shift_blocktri.hip) up to kMaxBlockBandwidth, else none.  The values are
-// those of mispec_symshift_path.  `iterative` (shift_minres.hip) is never the answer of shift_path: an operator takes it only when
-// its solver kind (option shift_solver, mispec_symshift_create_solver) asks for it.
+// those of mispec_symshift_path.  `iterative` (shift_minres.hip; shift_bicgstab.hip for a general operator) is never the answer of
+// shift_path: an operator takes it only when its solver kind (option shift_solver, mispec_symshift_create_solver,
+// mispec_symshift_create_general_solver) asks for it.
 enum class ShiftPath { unsupported = -1, inverse = 0, chunk = 1, blocktri = 2, iterative = 3 };
 inline ShiftPath shift_path(int64_t n, int64_t b)
 {
@@ -37,7 +38,17 @@ struct BlockTri
     DevBuf<unsigned long long> record;  // [0] zero pivot columns, [1] bits of the smallest |pivot| / max |S_i|
     size_t factor_bytes() const { return 2 * size_t(N) * size_t(s) * size_t(s) * sizeof(double); }
 };
-struct ShiftMinres;  // the iterative path's operator, vectors and counters (shift_minres.hip)
+struct ShiftIterative;  // the iterative path: what its two Krylov methods share (operator, counters; shift_iterative_state.hpp),
+struct ShiftMinres;     // MINRES for symmetric operators and pencils (shift_minres.hip),
+struct ShiftBicgstab;   // BiCGStab for general operators (shift_bicgstab.hip)
+// the rule of a general operator (mispec_symshift_general_solver_path): the dense inverse up to kMaxDense under direct and auto,
+// beyond it nothing (direct) or the iterative path (auto); iterative takes that path at every n
+inline ShiftPath general_shift_path(int64_t n, ShiftSolverKind kind)
+{
+    if (kind != ShiftSolverKind::iterative && n <= kMaxDense)
+        return ShiftPath::inverse;
+    return kind == ShiftSolverKind::direct ? ShiftPath::unsupported : ShiftPath::iterative;
+}
 }  // namespace mispec
 
 struct mispec_symshift
@@ -55,7 +66,8 @@ struct mispec_symshift
     int band_b = 0;
     // pencil form (SymShiftInvert, MatOp/SymShiftInvert.h:140-208): the operator is (A - sigma B)^{-1}; B is kept the
     // same way as A (band on host + device, or triplets for the dense path).  Empty: B = I.
-    // general (non-symmetric) matrix — SparseGenRealShiftSolve: every stored entry is used as it is; dense path only
+    // general (non-symmetric) matrix — SparseGenRealShiftSolve: every stored entry is used as it is; the dense path, or the
+    // iterative one (bicgstab below)
     bool general = false;
     bool pencil = false;
     std::vector<double> bandB0;
@@ -67,10 +79,13 @@ struct mispec_symshift
     bool dense = false;
     std::unique_ptr<mispec::BandLevel> top;  // banded path
     std::unique_ptr<mispec::BlockTri> blocktri;  // block-tridiagonal path (65 <= band_b <= 512 beyond the dense limit)
-    std::unique_ptr<mispec::ShiftMinres> minres;  // iterative path: set at construction, no band and no triplets are kept then
-    mispec::ShiftPath path() const  // a general (non-symmetric) operator has the explicit inverse only
+    // iterative path: one of the two is set at construction, and no band and no triplets are kept then
+    std::unique_ptr<mispec::ShiftMinres> minres;      // symmetric operator or pencil
+    std::unique_ptr<mispec::ShiftBicgstab> bicgstab;  // general operator
+    mispec::ShiftIterative* iterative() const;        // whichever is set, or nullptr on a direct path
+    mispec::ShiftPath path() const  // a general (non-symmetric) operator has the explicit inverse as its only direct path
     {
-        if (minres)
+        if (minres || bicgstab)
             return mispec::ShiftPath::iterative;
         if (general)
             return n <= mispec::kMaxDense ? mispec::ShiftPath::inverse : mispec::ShiftPath::unsupported;
@@ -135,6 +150,11 @@ struct TriangleView
 void minres_create(mispec_symshift& S, const TriangleView& A, const TriangleView& B);
 void minres_set_shift(mispec_symshift& S, double sigma);
 void minres_solve(const mispec_symshift& S, const double* x_dev, double* y_dev, bool probe = false);
+// The same three for a general operator (shift_bicgstab.hip): right-preconditioned BiCGStab on A - sigma I with the products of
+// the CSR operator the SpMV's general ingest builds from the compressed input (row_major as for mispec_symshift_create_general).
+void bicgstab_create(mispec_symshift& S, const int32_t* outer, const int32_t* inner, const double* val, int row_major);
+void bicgstab_set_shift(mispec_symshift& S, double sigma);
+void bicgstab_solve(const mispec_symshift& S, const double* x_dev, double* y_dev, bool probe = false);
 // the probe right-hand side of set_shift's calibration: deterministic values in (-0.5, 0.5), on the context stream
 void launch_probe_fill(const mispec_ctx& ctx, int64_t n, double* v_dev);
 // the cut of k columns: widths 4 / 2 / 1, widest first.  panel: 0 = what option shift_block says, 1 = single columns, 2 | 4 = the
