@@ -602,6 +602,41 @@ int mispec_fac_orth_info(const mispec_fac* fac, int* mode, int64_t* lagged_steps
  * applies a pending correction first; f_norm() reports sqrt(|f~|^2 - |c|^2) until then.  mispec_fac_restart_info counts the
  * restarts that went the fused way and those that were followed by further corrections. */
 int mispec_fac_restart_info(const mispec_fac* fac, int64_t* fused, int64_t* recorrected);
+/* Test hooks (tests/lagged_checks.py; never called by the library): ONE pass of the one-sweep path alone, on the caller's data,
+ * through the launchers and with the arguments the factorisation uses; every call allocates its scratch and synchronises.
+ * Vectors are device arrays of ld doubles per column, 16-byte aligned, ld even and >= n.  CONTRACT (the factorisation's own
+ * buffers are zero-filled and ld = n rounded up to even): for an odd n, row n of every vector a pass READS (V, f, src; V, ftilde)
+ * must be 0 — it is loaded as the second half of the last 16-byte row pair —, and row n of every vector it WRITES is written
+ * (with 0); rows from n rounded up to even onward are neither read nor written.
+ *
+ * mispec_lagged_pass: step i of lanczos_step_lagged — launch_orth(ORTH_LAGGED) on V[:, :i], then the reduction of its record with
+ * the tail kFinishLagged.  f_dev is read as the residual and overwritten with the next one (the factorisation's aliasing);
+ * vout_dev receives column i; src_dev is w, or (flags_in[1]) u = A f~ of the one-reduction form.  c_in_host: i coefficients
+ * (also the tail's accepted V'f of step i-1).  alpha_count > 0: the one-reduction tail runs on these partial sums of <f~, u>.
+ *   scal_in[6]   alpha (the device scalar <v_i, w>), beta (StepState::beta), lag_chk_max, lag_rel_c_max, lag_limit, order of the
+ *                operator (for beta < eps sqrt(n))
+ *   flags_in[6]  pending (StepState::lag_pending), onered (form of src), status on entry, lag_last, lag_steps, onered_steps
+ *   pstride      stride of the partial records (0: the factorisation's 8 CUs + 8); the records start out as NaN
+ *   diag_host, subd_host   i + 1 entries each of StepState::diag / subd, in and out
+ *   red_host     1032 doubles, in and out: the reduced record — slots [0, i) c, i <v_i, f>, [i+1, 2i+1) chk, 1024 sum f^2,
+ *                1025 max |f|, 1026 its root, 1027 max |c|
+ *   scal_out[7]  StepState beta, alpha, lag_chk_max, lag_rel_c_max, err, 0, and the alpha scalar after the tail (alpha~)
+ *   int_out[9]   status, stop_step, stop_count, count, need_corr, lag_pending, lag_steps, onered_steps, records of the pass
+ * MISPEC_EINVAL: i < 1 or 2 i + 1 > 1024, ld < n or odd, a record stride smaller than the grid, NULL or misaligned vectors.
+ *
+ * mispec_fused_restart_pass: launch_vq_fused in place (X = V: V[:, :p] <- V[:, :m] Q, Q_host m x p column-major) with the pending
+ * correction riding on it, then the reduction with the tail kFinishFusedRestart, as mispec_fac_restart_sym runs them (there
+ * p = k + 1, kcol = k).  fnew_dev must not alias ftilde_dev.  force_check: MISPEC_ORTH_TEST_RESTART_CHECK.
+ *   red_host     1032 doubles, in and out: slots [0, m) V'f_corr, m |fnew|^2, 1024 |f_corr|^2, 1026 its root, 1027 max |V'f_corr|
+ *   scal_out[3]  StepState beta, rst_err, rst_beta_corr;  int_out[4]  status, stop_step, stop_count, records of the pass
+ * MISPEC_EINVAL: not 1 <= p <= m <= 64, kcol outside [0, p), ld < n or odd, a record stride smaller than the grid. */
+int mispec_lagged_pass(mispec_ctx* ctx, const double* V_dev, int64_t ldv, int i, int64_t n, double* f_dev, const double* src_dev,
+                       double* vout_dev, const double* c_in_host, const double* alpha_parts_host, int64_t alpha_count,
+                       const double* scal_in, const int* flags_in, int64_t pstride, double* diag_host, double* subd_host,
+                       double* red_host, double* scal_out, int64_t* int_out);
+int mispec_fused_restart_pass(mispec_ctx* ctx, double* V_dev, int64_t ldv, int m, int64_t n, const double* Q_host, int p,
+                              const double* c_host, const double* ftilde_dev, double* fnew_dev, double q_last, double h_sub, int kcol,
+                              int status_in, int force_check, int64_t pstride, double* red_host, double* scal_out, int64_t* int_out);
 /* The host turns of the restarts (HermEigsBase.h:105-155 between two factorize_from calls): how many were timed, the host seconds
  * between "state of the finished sweep seen" and "restart enqueued" summed over them, and how often the pinned-memory hand-off
  * fell back to a copy (option host_turn). */

@@ -1505,6 +1505,86 @@ def lobpcg_block_sub(Z, Y, Cmat, n, ctx=None):
     check(lib().mispec_lobpcg_block_sub(ctx.h, C.c_void_p(zp), ldz, q, C.c_void_p(yp), ldy, c, _dp(Cm), int(n)))
 
 
+RECORD_LD = 1032  # doubles of a reduced record (csrc/krylov.hpp kPartialLd): slots 0 ... 1023, sum f^2, max |f|, its root, max |c|
+SLOT_BETA2, SLOT_MAXABS, SLOT_BETA, SLOT_ERR = 1024, 1025, 1026, 1027
+STEP_OK, STEP_SMALL_BETA, STEP_MORE_CORR, STEP_TINY_F, STEP_LAG_CHECK, STEP_RESTART_CHECK = range(6)  # krylov.hpp kStep*
+
+
+def lagged_pass(V, i, n, f, src, vout, c_in, alpha, beta, *, pending, onered, diag, subd, status=STEP_OK, lag_last=False,
+                lag_chk_max=0.0, lag_rel_c_max=0.0, lag_limit=1e-6, n_op=None, lag_steps=0, onered_steps=0, alpha_parts=None,
+                pstride=0, red=None, ctx=None):
+    """TEST HOOK (mispec_lagged_pass, include/mispec.h): step i of the one-sweep Lanczos path alone — the ORTH_LAGGED pass over
+    V[:, :i] chosen by the library's own dispatch, the reduction of its record and the scalar tail — on the caller's data.
+    V: torch block (see _torch_block) of at least i columns; f, src, vout: 1-D float64 CUDA tensors of at least ld entries' worth
+    of rows (f is overwritten with the next residual, vout with column i).  Contract for an odd n: row n of V, f and src is 0.
+    diag, subd: at least i + 1 entries of H's diagonals; red: the record on entry (RECORD_LD doubles, default zeros).
+    Returns a dict: red, diag, subd (numpy) and the scalars the tail leaves."""
+    import torch
+
+    ctx = ctx or default_context()
+    vp, ldv, ncols = _torch_block(V, "lagged_pass")
+    if ncols < i:
+        raise ValueError("lagged_pass: V has fewer than i columns")
+    for t in (f, src, vout):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("lagged_pass: f, src and vout must be contiguous 1-D float64 CUDA tensors")
+    c_in = _f64(c_in)
+    if c_in.shape != (max(i, 0),):
+        raise ValueError("lagged_pass: one coefficient per finished column")
+    d, s = np.zeros(max(i, 0) + 1), np.zeros(max(i, 0) + 1)
+    d[:] = _f64(diag)[: d.size]
+    s[:] = _f64(subd)[: s.size]
+    rec = np.zeros(RECORD_LD) if red is None else _f64(red).copy()
+    if rec.shape != (RECORD_LD,):
+        raise ValueError("lagged_pass: a record has RECORD_LD doubles")
+    parts = _f64(alpha_parts) if alpha_parts is not None else None
+    scal = _f64([alpha, beta, lag_chk_max, lag_rel_c_max, lag_limit, float(n if n_op is None else n_op)])
+    flags = _i32([int(pending), int(onered), int(status), int(bool(lag_last)), int(lag_steps), int(onered_steps)])
+    so, io = np.zeros(7), np.zeros(9, dtype=np.int64)
+    _torch_sync()
+    check(lib().mispec_lagged_pass(ctx.h, C.c_void_p(vp), ldv, int(i), int(n), C.c_void_p(f.data_ptr()), C.c_void_p(src.data_ptr()),
+                                   C.c_void_p(vout.data_ptr()), _dp(c_in), _dp(parts), 0 if parts is None else int(parts.size),
+                                   _dp(scal), _ip(flags), int(pstride), _dp(d), _dp(s), _dp(rec), _dp(so),
+                                   io.ctypes.data_as(C.POINTER(C.c_int64))))
+    return dict(red=rec, diag=d, subd=s, beta=so[0], alpha=so[1], lag_chk_max=so[2], lag_rel_c_max=so[3], err=so[4], alpha_out=so[6],
+                status=int(io[0]), stop_step=int(io[1]), stop_count=int(io[2]), count=int(io[3]), need_corr=int(io[4]),
+                lag_pending=int(io[5]), lag_steps=int(io[6]), onered_steps=int(io[7]), nrec=int(io[8]))
+
+
+def fused_restart_pass(V, m, n, Q, c, ftilde, fnew, q_last, h_sub, kcol, *, status=STEP_OK, force_check=False, pstride=0, red=None,
+                       ctx=None):
+    """TEST HOOK (mispec_fused_restart_pass, include/mispec.h): the restart's V*Q pass with the pending correction riding on it
+    (k_vq_fused, in place: V[:, :p] <- V[:, :m] Q) and the reduction with its tail, as mispec_fac_restart_sym runs them.
+    V: torch block of at least m columns; Q: m x p array; c: m coefficients; ftilde, fnew: 1-D float64 CUDA tensors (distinct).
+    Contract for an odd n: row n of V and ftilde is 0.  Returns a dict: red (numpy) and the scalars the tail leaves."""
+    import torch
+
+    ctx = ctx or default_context()
+    vp, ldv, ncols = _torch_block(V, "fused_restart_pass")
+    if ncols < m:
+        raise ValueError("fused_restart_pass: V has fewer than m columns")
+    for t in (ftilde, fnew):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("fused_restart_pass: ftilde and fnew must be contiguous 1-D float64 CUDA tensors")
+    Qm = np.asfortranarray(Q, dtype=np.float64)
+    if Qm.ndim != 2 or Qm.shape[0] != m:
+        raise ValueError("fused_restart_pass: Q must be m x p")
+    c = _f64(c)
+    if c.shape != (max(m, 0),):
+        raise ValueError("fused_restart_pass: one coefficient per column")
+    rec = np.zeros(RECORD_LD) if red is None else _f64(red).copy()
+    if rec.shape != (RECORD_LD,):
+        raise ValueError("fused_restart_pass: a record has RECORD_LD doubles")
+    so, io = np.zeros(3), np.zeros(4, dtype=np.int64)
+    _torch_sync()
+    check(lib().mispec_fused_restart_pass(ctx.h, C.c_void_p(vp), ldv, int(m), int(n), _dp(Qm), int(Qm.shape[1]), _dp(c),
+                                          C.c_void_p(ftilde.data_ptr()), C.c_void_p(fnew.data_ptr()), float(q_last), float(h_sub),
+                                          int(kcol), int(status), int(bool(force_check)), int(pstride), _dp(rec), _dp(so),
+                                          io.ctypes.data_as(C.POINTER(C.c_int64))))
+    return dict(red=rec, beta=so[0], rst_err=so[1], rst_beta_corr=so[2], status=int(io[0]), stop_step=int(io[1]),
+                stop_count=int(io[2]), nrec=int(io[3]))
+
+
 class _GEigsCholeskyOp:
     """MatOp/internal/SymGEigsCholeskyOp.h: y = L^{-1} A L^{-T} x."""
 

@@ -301,6 +301,11 @@ SIGNATURES = {
     "mispec_fac_set_orth_mode": (C.c_int, [_vp, C.c_int]),
     "mispec_fac_orth_info": (C.c_int, [_vp, C.POINTER(C.c_int), _lp, _lp, _lp, _dp, _dp]),
     "mispec_fac_restart_info": (C.c_int, [_vp, _lp, _lp]),
+    # test hooks: one pass of the one-sweep path on the caller's data (tests/lagged_checks.py)
+    "mispec_lagged_pass": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, _vp, _vp, _vp, _dp, _dp, C.c_int64, _dp, _ip, C.c_int64,
+                                     _dp, _dp, _dp, _dp, _lp]),
+    "mispec_fused_restart_pass": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, _dp, C.c_int, _dp, _vp, _vp, C.c_double, C.c_double,
+                                            C.c_int, C.c_int, C.c_int, C.c_int64, _dp, _dp, _lp]),
     "mispec_fac_turn_info": (C.c_int, [_vp, _lp, _dp, _lp]),
     "mispec_symeigs_turn_info": (C.c_int, [_vp, _lp, _dp, _lp]),
     "mispec_set_option": (C.c_int, [C.c_char_p, C.c_char_p]),

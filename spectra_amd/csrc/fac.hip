@@ -15,6 +15,7 @@
 #include "csr.hpp"
 #include "dense.hpp"
 #include "krylov.hpp"
+#include "lagged_args.hpp"
 #include <chrono>
 #include "cholesky.hpp"
 #include "reginv.hpp"
@@ -1158,9 +1159,8 @@ void lanczos_step_lagged(mispec_fac& F, int i, bool last, bool defer)
         apply_op(F, F.f.p, F.w.p, true, nullptr, 0.0, nullptr, &st->status);
         F.skip_alpha_reduce = false;
         FinishArgs fin = F.lag_def.fin;
-        fin.alpha_parts = F.alpha_partials.p;
-        fin.alpha_count = (F.A && !F.Chol) ? spmv_num_blocks(F.nloc) : lanczos_epilogue_records(*F.ctx, F.nloc);
-        fin.alpha_out = F.alpha_slot();
+        lagged_onered_args(fin, F.alpha_partials.p,
+                           (F.A && !F.Chol) ? spmv_num_blocks(F.nloc) : lanczos_epilogue_records(*F.ctx, F.nloc), F.alpha_slot());
         {
             Timed t(F, FAM_VTF, nullptr, false);
             Timed t2(F, FAM_REDUCE);
@@ -1184,27 +1184,11 @@ void lanczos_step_lagged(mispec_fac& F, int i, bool last, bool defer)
     }
 
     const int cur = i & 1;
-    FinishArgs fin;
-    fin.st = st;
-    fin.step = i;
-    fin.eps = kEps;
-    fin.beta_thresh = kEps * std::sqrt(double(F.n));
-    fin.eps_sqrt = std::sqrt(kEps);
-    fin.lag_limit = F.lag_limit;
-    fin.lag_last = (last && !defer) ? 1 : 0;
-    fin.max_spec = speculative_corrections(F);
+    // (arguments: lagged_args.hpp, shared with the test hook mispec_lagged_pass)
+    FinishArgs fin = lagged_finish_args(st, i, F.n, F.lag_limit, last && !defer, speculative_corrections(F), F.alpha_slot(),
+                                        F.red_buf(cur ^ 1));
     {
-        OrthArgs a = orth_args(F, i);
-        a.src = F.w.p;
-        a.vi = F.f.p;
-        a.dst = F.f.p;
-        a.vout = v;
-        a.c_in = F.red_buf(cur ^ 1);
-        a.alpha_dev = F.alpha_slot();
-        a.beta_dev = &st->beta;
-        a.pending = &st->lag_pending;
-        a.status = &st->status;
-        a.onered = onered ? 1 : 0;
+        const OrthArgs a = lagged_orth_args(orth_args(F, i), F.w.p, F.f.p, v, F.red_buf(cur ^ 1), F.alpha_slot(), st, onered);
         Timed t(F, FAM_VTF);
         if (i < 2 * kPanelCols)
             F.count_bytes(FAM_VTF, i + 4);  // i columns, f and w read; column i and f written
@@ -1217,9 +1201,6 @@ void lanczos_step_lagged(mispec_fac& F, int i, bool last, bool defer)
             F.count_bytes(FAM_VTF, 2 * rest + 4 * (rest / kPanelCols) + (i - rest) + 4);
         }
         const int nrec = launch_orth(*F.ctx, ORTH_LAGGED, a);
-        fin.mode = kFinishLagged;
-        fin.alpha_src = F.alpha_slot();
-        fin.prev_red = F.red_buf(cur ^ 1);
         // the plain matrix product on bases of one column panel; the last step of a sweep is reduced at once (what follows — the
         // reference's corrections or the restart — needs its record)
         // (every operator the library applies itself: matrices incl. the SVD product and the Cholesky mode of the generalized
@@ -2446,15 +2427,7 @@ extern "C" int mispec_fac_restart_sym(mispec_fac* fac, const double* shifts_host
                 // One-sweep steps: the last step's correction f = ftilde - V c and the reference's test of the result (Lanczos.h:
                 // 156: max |V'f| <= eps |f|) ride on the V*Q pass (k_vq_fused) — one sweep over the basis instead of two.
                 F.end_pending = false;
-                VqFusedArgs fa;
-                fa.c = F.red_buf(F.end_rec);
-                fa.ftilde = F.f.p;
-                fa.fnew = F.tmp.p;
-                fa.q_last = q_last;
-                fa.h_sub = h_sub;
-                fa.kcol = k;
-                fa.partials = F.partials.p;
-                fa.pstride = F.pstride;
+                const VqFusedArgs fa = fused_restart_args(F.red_buf(F.end_rec), F.f.p, F.tmp.p, q_last, h_sub, k, F.partials.p, F.pstride);
                 if (no_sync && !fast)
                 {
                     StepState& st0 = *F.h_state.p;
@@ -2475,11 +2448,8 @@ extern "C" int mispec_fac_restart_sym(mispec_fac* fac, const double* shifts_host
                 }
                 if (no_sync)
                 {
-                    FinishArgs fin;
-                    fin.mode = kFinishFusedRestart;
-                    fin.st = F.d_state.p;
-                    fin.step = k;
-                    fin.eps = F.test_restart_check ? -1.0 : kEps;  // (the hook: max |V'f| > -|f| always holds)
+                    // (the hook test_restart_check: max |V'f| > -|f| always holds)
+                    const FinishArgs fin = fused_restart_finish_args(F.d_state.p, k, F.test_restart_check ? -1.0 : kEps);
                     reduce_record(F, nrec, m + 1, F.end_rec ^ 1, fin);
                     if (F.turn_open)
                     {
