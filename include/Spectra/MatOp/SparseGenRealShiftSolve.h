@@ -29,7 +29,13 @@ private:
     internal::CtxPtr m_ctx;
     std::shared_ptr<mispec_symshift> m_solver;
 
-    void ingest(const SparseView<Scalar, StorageIndex>& A, ShiftSolver solver)
+protected:
+    // the constructor of the C ABI an operator is built by: mispec_symshift_create_general_solver here, another one in
+    // SparseGenComplexShiftSolve
+    using Creator = int (*)(mispec_ctx*, int64_t, const int32_t*, const int32_t*, const double*, int, int, mispec_symshift**);
+
+private:
+    void ingest(const SparseView<Scalar, StorageIndex>& A, ShiftSolver solver, Creator create = &mispec_symshift_create_general_solver)
     {
         if (A.rows != A.cols)
             throw std::invalid_argument("SparseGenRealShiftSolve: matrix must be square");
@@ -39,9 +45,15 @@ private:
         mispec_symshift* raw = nullptr;
         const std::size_t nnz = static_cast<std::size_t>(A.outer[A.rows]);
         const internal::Int32Indices<StorageIndex> outer(A.outer, static_cast<std::size_t>(A.rows) + 1), inner(A.inner, nnz);
-        internal::check(mispec_symshift_create_general_solver(m_ctx.get(), A.rows, outer.data(), inner.data(), A.values, A.row_major ? 1 : 0,
-                                                              static_cast<int>(solver), &raw));
+        internal::check(create(m_ctx.get(), A.rows, outer.data(), inner.data(), A.values, A.row_major ? 1 : 0, static_cast<int>(solver), &raw));
         m_solver = std::shared_ptr<mispec_symshift>(raw, [](mispec_symshift* p) { (void) mispec_symshift_destroy(p); });
+    }
+
+protected:
+    SparseGenRealShiftSolve(const SparseView<Scalar, StorageIndex>& mat, internal::CtxPtr ctx, ShiftSolver solver, Creator create) :
+        m_ctx(ctx ? ctx : internal::default_context())
+    {
+        ingest(mat, solver, create);
     }
 
 public:
@@ -53,9 +65,25 @@ public:
     }
 
 #ifdef MISPEC_HAVE_EIGEN
+protected:
+    template <typename Derived>
+    SparseGenRealShiftSolve(const Eigen::SparseMatrixBase<Derived>& mat, ShiftSolver solver, Creator create) :
+        m_ctx(internal::default_context())
+    {
+        ingest_eigen(mat, solver, create);
+    }
+
+public:
     template <typename Derived>
     SparseGenRealShiftSolve(const Eigen::SparseMatrixBase<Derived>& mat, ShiftSolver solver = ShiftSolver::Default) :
         m_ctx(internal::default_context())
+    {
+        ingest_eigen(mat, solver, &mispec_symshift_create_general_solver);
+    }
+
+private:
+    template <typename Derived>
+    void ingest_eigen(const Eigen::SparseMatrixBase<Derived>& mat, ShiftSolver solver, Creator create)
     {
         using Plain = Eigen::SparseMatrix<Scalar, Flags, StorageIndex>;
         static_assert(static_cast<int>(Derived::PlainObject::IsRowMajor) == static_cast<int>(Plain::IsRowMajor),
@@ -69,8 +97,10 @@ public:
         v.inner = tmp.innerIndexPtr();
         v.values = tmp.valuePtr();
         v.row_major = Plain::IsRowMajor;
-        ingest(v, solver);
+        ingest(v, solver, create);
     }
+
+public:
 #endif
 
     // adopt a solver created through the C ABI (not owned)

@@ -412,7 +412,8 @@ int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const int32_t* ou
  * ITERATION counted there is one BiCGStab iteration, which is TWO products with A (a MINRES iteration is one).  A breakdown of
  * the recurrence ends a pass and the solve restarts from the explicit residual; it is no error.  No factor and no triplets are
  * kept: 12 work vectors of n doubles.  mispec_symshift_set_shift_complex refuses such a handle (MISPEC_EINVAL): complex shifts
- * need the dense path.  The eigensolvers take their steps host-driven on it. */
+ * need the dense path, or a handle of mispec_symshift_create_general_complex (mispec_extras.h), whose iterative path runs
+ * BiCGStab in complex arithmetic.  The eigensolvers take their steps host-driven on it. */
 int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
                                           const double* val_host, int row_major, int solver, mispec_symshift** out);
 /* The path mispec_symshift_create_general_solver takes for dimension n under a solver kind (host arithmetic only, no device):

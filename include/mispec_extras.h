@@ -73,8 +73,24 @@ int mispec_davidson_eigenvalues(const mispec_davidson* S, double* out_host);    
 int mispec_davidson_eigenvectors(const mispec_davidson* S, double* out_host, int64_t ld);    /* n x nev, column-major */
 
 /* Complex shift for the general operator (mispec_symshift_create_general): afterwards solve = Re((A - sigma I)^{-1} x), the
- * operator of GenEigsComplexShiftSolver (MatOp/SparseGenComplexShiftSolve.h:74-113, DenseGenComplexShiftSolve.h).  n <= 4096. */
+ * operator of GenEigsComplexShiftSolver (MatOp/SparseGenComplexShiftSolve.h:74-113, DenseGenComplexShiftSolve.h).  n <= 4096 on
+ * the dense path; any n on the iterative path of a handle of mispec_symshift_create_general_complex. */
 int mispec_symshift_set_shift_complex(mispec_symshift* S, double sigmar, double sigmai);
+/* The general operator for complex shifts, with a solver kind: 0 direct (the dense path; n > 4096 refused), 1 auto (dense up to
+ * n = 4096, iterative beyond), 2 iterative (for every n >= 1); anything else, -1 included, is MISPEC_EINVAL (option shift_solver
+ * is not read).  Arguments, refusals and the operator built are those of mispec_symshift_create_general_solver.  On the ITERATIVE
+ * PATH (path 3) mispec_symshift_set_shift_complex(sigmar, sigmai != 0) applies y = Re((A - sigma I)^{-1} x) by right-preconditioned
+ * BiCGStab in complex arithmetic with the complex Jacobi preconditioner 1 / (diag A - sigma) (csrc/shift_zbicgstab.hip): A stays
+ * real, a complex product is two real ones, and acceptance, restarts, refusal of a shift whose probe solve does not converge,
+ * settings and counters are those of the real method; one ITERATION is two complex products.  A real shift
+ * (mispec_symshift_set_shift, or sigmai == 0) runs the real BiCGStab of mispec_symshift_create_general_solver on the same
+ * operator, and a handle goes back and forth between the two.  24 more work vectors of n doubles (12 complex ones, two planes
+ * each) from the first complex shift on. */
+int mispec_symshift_create_general_complex(mispec_ctx* ctx, int64_t n, const int32_t* outer_host, const int32_t* inner_host,
+                                           const double* val_host, int row_major, int solver, mispec_symshift** out);
+/* The path that constructor takes for dimension n under a solver kind (host arithmetic only): 0 or 3; MISPEC_EINVAL with the
+ * constructor's wording where it refuses (direct, n > 4096), and for n < 1 or a solver outside 0 ... 2. */
+int mispec_symshift_general_complex_solver_path(int64_t n, int solver);
 
 /* The shift modes of the generalized solver (SymGEigsShiftSolver.h:36-207): operator y = (A - sigma B)^{-1} M x in the
  * B-inner product, with S the pencil solver of mispec_symshift_create_pencil (shift already set), B the matrix of the

@@ -22,7 +22,7 @@ __all__ = ["SortRule", "CompInfo", "Context", "SparseSymMatProd", "SparseGenMatP
            "Factorization", "tridiag_qr", "tridiag_eigen", "hess_qr", "double_shift_qr", "hess_schur", "hess_eigen", "MispecError", "build_library", "shard_range", "BAND_OFFSETS", "SYNTH_SEED",
            "SparseHermMatProd", "DenseHermMatProd", "HermEigsSolver", "spmm_plan", "shift_block_plan", "dia_sym_plan", "mirror_triangle_device",
            "LOBPCGSolver", "LOBPCGInfo", "lobpcg_gram", "lobpcg_resid", "lobpcg_block_sub", "shift_solver_path",
-           "general_shift_solver_path"]
+           "general_shift_solver_path", "general_complex_shift_solver_path"]
 
 BAND_OFFSETS = (1, 2, 3, 1000, 1001, 100000, 100001)  # SURVEY.md §8(d) "M-band": 15 nnz/row with the diagonal
 SYNTH_SEED = 20240607
@@ -330,6 +330,18 @@ def general_shift_solver_path(n, solver=None):
     """The path a general (non-symmetric) shift-and-invert operator of this size takes under a solver kind
     (mispec_symshift_general_solver_path; host only): 0 inverse, 3 iterative; ValueError where construction would refuse."""
     rc = lib().mispec_symshift_general_solver_path(int(n), _shift_solver_kind(solver))
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def general_complex_shift_solver_path(n, solver):
+    """The path SparseGenComplexShiftSolve(complex_solver=solver) takes at this size (mispec_symshift_general_complex_solver_path;
+    host only): 0 inverse, 3 iterative (BiCGStab in complex arithmetic); ValueError where construction would refuse.  solver is
+    one of direct | auto | iterative: option shift_solver is not read."""
+    if solver is None:
+        raise ValueError("unknown shift solver None: one of %s" % ", ".join(SHIFT_SOLVERS))
+    rc = lib().mispec_symshift_general_complex_solver_path(int(n), _shift_solver_kind(solver))
     if rc < 0:
         check(rc)
     return rc
@@ -1836,14 +1848,29 @@ class GenEigsRealShiftSolver(GenEigsSolver):
         super().__init__(_GenShiftBinding(op, sigma), nev, ncv)
 
 class SparseGenComplexShiftSolve(SparseGenRealShiftSolve):
-    """MatOp/SparseGenComplexShiftSolve.h: y = Re((A - sigma I)^{-1} x) for a general sparse A and a complex shift (n <= 4096).
-    The dense path only: a solver kind other than direct is refused, and option shift_solver is not read."""
+    """MatOp/SparseGenComplexShiftSolve.h: y = Re((A - sigma I)^{-1} x) for a general sparse A and a complex shift.
+    complex_solver: None | "direct" (the dense path, n <= 4096) | "auto" (that, and beyond n = 4096 the iterative path:
+    Jacobi-preconditioned BiCGStab in complex arithmetic for a complex shift, the real one for a real shift) | "iterative"
+    (include/mispec_extras.h mispec_symshift_create_general_complex).  solver: a kind other than direct is refused — the operator
+    that argument selects takes real shifts only; option shift_solver is not read."""
 
-    def __init__(self, mat, ctx=None, solver=None):
+    def __init__(self, mat, ctx=None, solver=None, complex_solver=None):
         if solver not in (None, "direct"):
             raise ValueError("SparseGenComplexShiftSolve: solver %r is not supported: the iterative path takes real shifts only "
-                             "(complex shifts need the dense path, solver='direct', n <= 4096)" % (solver,))
-        super().__init__(mat, ctx, "direct")
+                             "(complex shifts need the dense path, solver='direct', n <= 4096, or complex_solver=)" % (solver,))
+        if complex_solver in (None, "direct"):
+            super().__init__(mat, ctx, "direct")
+            return
+        kind = _shift_solver_kind(complex_solver)
+        self.ctx = ctx or default_context()
+        n, nc, outer, inner, val, row_major = _compressed(mat)
+        if n != nc:
+            raise ValueError("SparseGenComplexShiftSolve: matrix must be square")
+        h = C.c_void_p()
+        check(lib().mispec_symshift_create_general_complex(self.ctx.h, n, _ip(outer), _ip(inner), _dp(val), int(row_major), kind,
+                                                           C.byref(h)))
+        self.h = h
+        self.n = n
 
     def set_shift(self, sigmar, sigmai=0.0):
         check(lib().mispec_symshift_set_shift_complex(self.h, float(sigmar), float(sigmai)))

@@ -325,6 +325,8 @@ SIGNATURES = {
     "mispec_symshift_create_general": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_int, _vpp]),
     "mispec_symshift_create_general_solver": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_int, C.c_int, _vpp]),
     "mispec_symshift_general_solver_path": (C.c_int, [C.c_int64, C.c_int]),
+    "mispec_symshift_create_general_complex": (C.c_int, [_vp, C.c_int64, _ip, _ip, _dp, C.c_int, C.c_int, _vpp]),
+    "mispec_symshift_general_complex_solver_path": (C.c_int, [C.c_int64, C.c_int]),
     "mispec_geneigs_destroy": (C.c_int, [_vp]),
     "mispec_geneigs_init": (C.c_int, [_vp, _dp]),
     "mispec_geneigs_compute": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_double, C.c_int, _lp]),

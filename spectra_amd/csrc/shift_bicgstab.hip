@@ -361,20 +361,25 @@ void bicgstab_create(mispec_symshift& S, const int32_t* outer, const int32_t* in
     S.bicgstab = std::move(M);
 }
 
+void bicgstab_alloc(mispec_symshift& S)
+{
+    ShiftBicgstab& M = *S.bicgstab;
+    if (M.minv.p)
+        return;
+    const size_t np = size_t(S.n) + 2;
+    alloc_shared(M, *S.ctx, S.n);
+    for (DevBuf<double>* v : {&M.rs, &M.rhat, &M.d, &M.dhat, &M.v, &M.shat, &M.t, &M.sol})
+        v->alloc(np);
+    M.state.alloc(1);
+    M.h_state.alloc(1);
+}
+
 void bicgstab_set_shift(mispec_symshift& S, double sigma)
 {
     ShiftBicgstab& M = *S.bicgstab;
     const mispec_ctx& ctx = *S.ctx;
     const int64_t n = S.n;
-    if (!M.minv.p)
-    {
-        const size_t np = size_t(n) + 2;
-        alloc_shared(M, ctx, n);
-        for (DevBuf<double>* v : {&M.rs, &M.rhat, &M.d, &M.dhat, &M.v, &M.shat, &M.t, &M.sol})
-            v->alloc(np);
-        M.state.alloc(1);
-        M.h_state.alloc(1);
-    }
+    bicgstab_alloc(S);
     form_preconditioner<true>(M, ctx, n, sigma, nullptr, nullptr);
     solve_probe(S, M, sigma, [&](const double* x, double* y) { bicgstab_solve(S, x, y, true); });
 }

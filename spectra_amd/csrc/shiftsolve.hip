@@ -35,6 +35,7 @@
 #include "shiftsolve.hpp"
 #include "shift_bicgstab.hpp"
 #include "shift_minres.hpp"
+#include "shift_zbicgstab.hpp"
 #include "reorder.hpp"
 #include "dense.hpp"
 
@@ -2356,6 +2357,8 @@ void shiftsolve(const mispec_symshift& S, const double* X, int64_t ldx, double* 
         for (int c = 0; c < K; c++)
             if (S.minres)
                 minres_solve(S, X + c * ldx, Y + c * ldy);
+            else if (S.complex_shift())
+                zbicgstab_solve(S, X + c * ldx, Y + c * ldy);
             else
                 bicgstab_solve(S, X + c * ldx, Y + c * ldy);
         return;
@@ -2730,11 +2733,15 @@ extern "C" int mispec_symshift_create(mispec_ctx* ctx, int64_t n, const int32_t*
 // SparseGenRealShiftSolve (MatOp/SparseGenRealShiftSolve.h:33-99): y = (A - sigma I)^{-1} x for a general sparse A.
 // The reference factors with Eigen::SparseLU; here the dense path is used (LU with partial pivoting, explicit inverse, GEMV) for
 // n <= 4096, and where the solver kind allows it the iterative path (BiCGStab, shift_bicgstab.hip), which keeps no triplets.
-extern "C" int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner,
-                                                     const double* val, int row_major, int solver, mispec_symshift** out)
+namespace {
+// complex_shifts: the handle of mispec_symshift_create_general_complex, whose iterative path takes complex shifts too
+int create_general_impl(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val, int row_major,
+                        int solver, bool complex_shifts, mispec_symshift** out)
 {
     return guarded([&] {
         MISPEC_REQUIRE(ctx && out && outer && n >= 1, "mispec_symshift_create_general: bad argument");
+        MISPEC_REQUIRE(!complex_shifts || (solver >= 0 && solver <= 2),
+                       "mispec_symshift_create_general_complex: solver is one of 0 direct, 1 auto, 2 iterative");
         const ShiftPath path = general_shift_path(n, solver_kind(solver));
         MISPEC_REQUIRE(path != ShiftPath::unsupported,
                        "SparseGenRealShiftSolve: only n <= 4096 is supported on the GPU (the reference uses a general sparse LU)");
@@ -2745,7 +2752,11 @@ extern "C" int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n,
         S->general = true;
         S->half_bandwidth = n;  // never the banded (symmetric) path
         if (path == ShiftPath::iterative)
+        {
             bicgstab_create(*S, outer, inner, val, row_major);
+            if (complex_shifts)
+                zbicgstab_create(*S);
+        }
         else
             for (int64_t o = 0; o < n; o++)
                 for (int32_t p = outer[o]; p < outer[o + 1]; p++)
@@ -2758,6 +2769,20 @@ extern "C" int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n,
                 }
         *out = S.release();
     });
+}
+}  // namespace
+
+extern "C" int mispec_symshift_create_general_solver(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner,
+                                                     const double* val, int row_major, int solver, mispec_symshift** out)
+{
+    return create_general_impl(ctx, n, outer, inner, val, row_major, solver, false, out);
+}
+// SparseGenComplexShiftSolve with a solver kind: the same operator; on the iterative path the handle takes complex shifts by
+// BiCGStab in complex arithmetic (shift_zbicgstab.hip) and real ones by the real method.  Option shift_solver is not read.
+extern "C" int mispec_symshift_create_general_complex(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner,
+                                                      const double* val, int row_major, int solver, mispec_symshift** out)
+{
+    return create_general_impl(ctx, n, outer, inner, val, row_major, solver, true, out);
 }
 extern "C" int mispec_symshift_create_general(mispec_ctx* ctx, int64_t n, const int32_t* outer, const int32_t* inner, const double* val,
                                               int row_major, mispec_symshift** out)
@@ -2861,6 +2886,16 @@ extern "C" int mispec_symshift_general_solver_path(int64_t n, int solver)
     return rc == MISPEC_OK ? path : rc;
 }
 
+extern "C" int mispec_symshift_general_complex_solver_path(int64_t n, int solver)
+{
+    if (solver < 0 || solver > 2)
+    {
+        set_last_error("mispec_symshift_general_complex_solver_path: solver is one of 0 direct, 1 auto, 2 iterative");
+        return MISPEC_EINVAL;
+    }
+    return mispec_symshift_general_solver_path(n, solver);
+}
+
 extern "C" int mispec_symshift_path_info(const mispec_symshift* S, int* path, int64_t* block_rows, int64_t* blocks, int64_t* factor_bytes)
 {
     return guarded([&] {
@@ -2934,6 +2969,7 @@ extern "C" int mispec_symshift_set_shift(mispec_symshift* S, double sigma)
         S->ctx->make_current();
         S->factored = false;
         S->sigma = sigma;
+        S->sigma_im = 0.0;
         const int64_t n = S->n;
         const ShiftPath path = S->path();
         if (path == ShiftPath::iterative)
@@ -3096,12 +3132,31 @@ extern "C" int mispec_symshift_set_shift_complex(mispec_symshift* S, double sigm
     return guarded([&] {
         MISPEC_REQUIRE(S, "mispec_symshift_set_shift_complex: NULL argument");
         MISPEC_REQUIRE(S->general && !S->pencil, "mispec_symshift_set_shift_complex: complex shifts are for the general (non-symmetric) operator");
-        MISPEC_REQUIRE(!S->bicgstab, "SparseGenComplexShiftSolve: the iterative path takes real shifts only (a complex shift needs the dense path: "
-                                     "solver direct, n <= 4096)");
+        MISPEC_REQUIRE(!S->bicgstab || S->zbicgstab,
+                       "SparseGenComplexShiftSolve: the iterative path takes real shifts only (a complex shift needs the dense path: "
+                       "solver direct, n <= 4096)");
         S->ctx->make_current();
         S->factored = false;
         S->sigma = sigmar;
         const int64_t n = S->n;
+        if (S->zbicgstab)
+        {
+            // mispec_symshift_create_general_complex on the iterative path: O(n) work and one probe solve, as for a real shift
+            S->dense = false;
+            S->sigma_im = 0.0;  // (in effect only once the probe is accepted: a refused shift leaves none)
+            PhaseTimer pt("zbicgstab_set_shift (preconditioner, probe solve)", n, 0);
+            try
+            {
+                zbicgstab_set_shift(*S, sigmar, sigmai);
+            }
+            catch (...)
+            {
+                S->sigma_im = 0.0;
+                throw;
+            }
+            S->factored = true;
+            return;
+        }
         MISPEC_REQUIRE(n <= kMaxDense, "SparseGenComplexShiftSolve: only n <= 4096 is supported on the GPU");
         typedef std::complex<double> Cx;
         std::vector<Cx> A(size_t(n) * n, Cx(0.0, 0.0)), inv;

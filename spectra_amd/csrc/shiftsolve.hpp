@@ -40,7 +40,8 @@ struct BlockTri
 };
 struct ShiftIterative;  // the iterative path: what its two Krylov methods share (operator, counters; shift_iterative_state.hpp),
 struct ShiftMinres;     // MINRES for symmetric operators and pencils (shift_minres.hip),
-struct ShiftBicgstab;   // BiCGStab for general operators (shift_bicgstab.hip)
+struct ShiftBicgstab;   // BiCGStab for general operators (shift_bicgstab.hip),
+struct ShiftZBicgstab;  // ... and what a handle for complex shifts adds to it: BiCGStab in complex arithmetic (shift_zbicgstab.hip)
 // the rule of a general operator (mispec_symshift_general_solver_path): the dense inverse up to kMaxDense under direct and auto,
 // beyond it nothing (direct) or the iterative path (auto); iterative takes that path at every n
 inline ShiftPath general_shift_path(int64_t n, ShiftSolverKind kind)
@@ -82,6 +83,12 @@ struct mispec_symshift
     // iterative path: one of the two is set at construction, and no band and no triplets are kept then
     std::unique_ptr<mispec::ShiftMinres> minres;      // symmetric operator or pencil
     std::unique_ptr<mispec::ShiftBicgstab> bicgstab;  // general operator
+    // a handle of mispec_symshift_create_general_complex on the iterative path has both: bicgstab (the operator, the counters, real
+    // shifts) and zbicgstab (complex shifts).  sigma_im != 0: a complex shift sigma + i sigma_im is in effect and the solves are
+    // zbicgstab's
+    std::unique_ptr<mispec::ShiftZBicgstab> zbicgstab;
+    double sigma_im = 0.0;
+    bool complex_shift() const { return zbicgstab && sigma_im != 0.0; }
     mispec::ShiftIterative* iterative() const;        // whichever is set, or nullptr on a direct path
     mispec::ShiftPath path() const  // a general (non-symmetric) operator has the explicit inverse as its only direct path
     {
@@ -155,6 +162,13 @@ void minres_solve(const mispec_symshift& S, const double* x_dev, double* y_dev, 
 void bicgstab_create(mispec_symshift& S, const int32_t* outer, const int32_t* inner, const double* val, int row_major);
 void bicgstab_set_shift(mispec_symshift& S, double sigma);
 void bicgstab_solve(const mispec_symshift& S, const double* x_dev, double* y_dev, bool probe = false);
+void bicgstab_alloc(mispec_symshift& S);  // the work vectors of bicgstab_set_shift, at the first shift of either kind
+// Complex shifts on such a handle (shift_zbicgstab.hip): zbicgstab_create marks a handle that bicgstab_create built;
+// zbicgstab_set_shift (sigmai != 0) forms the complex Jacobi preconditioner and solves the probe; zbicgstab_solve is
+// y = Re((A - (sigma + i sigma_im) I)^{-1} x).  Errors as above.
+void zbicgstab_create(mispec_symshift& S);
+void zbicgstab_set_shift(mispec_symshift& S, double sigmar, double sigmai);
+void zbicgstab_solve(const mispec_symshift& S, const double* x_dev, double* y_dev, bool probe = false);
 // the probe right-hand side of set_shift's calibration: deterministic values in (-0.5, 0.5), on the context stream
 void launch_probe_fill(const mispec_ctx& ctx, int64_t n, double* v_dev);
 // the cut of k columns: widths 4 / 2 / 1, widest first.  panel: 0 = what option shift_block says, 1 = single columns, 2 | 4 = the
